@@ -16,8 +16,11 @@ one), reported under "gather".  Launch: `python -m torch.distributed.run --nproc
 bench.py --gpus N ...`; a bare `python bench.py --gpus N` starts those N ranks itself (as child
 processes, before anything touches the GPU) and relays rank 0's JSON line.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed on the launch stream) and `cpu_baseline` (the CPU oracle on a bounded sample).
+Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed on the launch stream, derived from the
+timed steps themselves).  A plain run sets up, warms up, times the --steps rollouts, writes their outputs when
+--dump-outputs DIR is given and prints that line; `--full` adds `cpu_baseline` (the CPU oracle on a bounded sample) and
+the extra legs (one-shot, hard mix, sweep, bounds, IPM only, PCIe, untabled shape, small batches, data_generation,
+latency), each of which takes runs of its own.
 """
 import argparse
 import json
@@ -53,10 +56,15 @@ def parse_args(argv=None):
     ap.add_argument("--mix", choices=["default", "hard"], default="default",
                     help="initial-state mix of the headline leg (hard: most steps constrained, lq_mpc_amd/synth.py)")
     ap.add_argument("--kernel", choices=["auto", "generic", "specialized", "workgroup"], default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the cpu_baseline leg and the extra legs (one-shot, hard mix, sweep, bounds, latency, ...); "
+                         "off by default: a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the timed path computed in its last step to DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="host threads of the cpu_baseline leg (default 16 = one GPU's share of the box's cores; 0 = every core this process may use)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra legs (one-shot, hard mix, sweep, latency)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra legs (one-shot, hard mix, sweep, latency)")
     ap.add_argument("--gather", choices=["final", "per-step"], default="final",
                     help="--gpus > 1: gather J_T once after the timed rollouts (default, north_star) or after every rollout")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
@@ -66,7 +74,32 @@ def parse_args(argv=None):
     ap.add_argument("--force-dist", action="store_true",
                     help="--gpus 1 only: initialise a world-size-1 process group and take the multi-rank code path (RCCL init on the "
                          "device, device-side all_gather_into_tensor, barrier, all_reduce) -- the calls an N-GPU launch makes")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: at most this many bytes in all (a fixed, seeded sample of the instances beyond it)
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes {name: array} as out_dir/<name>.npy in float64.  The instance axis is the last one of every array; when the
+    arrays hold more than DUMP_MAX_BYTES, the same seeded sample of instances is kept in all of them and its indices are
+    written as sample_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        n = next(iter(arrays.values())).shape[-1]
+        keep = min(n, DUMP_MAX_BYTES // (total // n + 8))          # (+ 8 bytes per kept instance for sample_index)
+        idx = np.sort(np.random.default_rng(20250404).choice(n, size=keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[..., idx]) for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 def spawn_ranks(args):
@@ -245,6 +278,8 @@ def main():
     iters_total, status_bad = totals()
     iters_mean = iters_total / qp_global
 
+    want_J = rank == 0 and (args.dump or (args.dump_outputs and args.mode == "rollout"))
+    J_all = None                                         # rank 0: the J_T curve of the last step over the global batch
     gather_info = None
     if distributed:
         gather_info = {"mode": args.gather, "world_size": world, "collective": "all_gather_into_tensor (lq_mpc_amd.dist.all_gather_costs)",
@@ -256,19 +291,29 @@ def main():
             gather_info["ms_final_gather_rank0"] = round(gathered["ms"], 4)
             gather_info["own_shard_intact"] = bool(torch.equal(mine, dJT))
             gather_info["J_T_sum"] = float(J.double().sum().item())
-            if args.dump and rank == 0:
-                np.save(args.dump, J.cpu().numpy())
+            if want_J:
+                J_all = J.cpu().numpy()
         else:
             k = (gathered["k"] - 1) & 1                  # the last per-step gather (flushed before the timed region closed)
             J = out_bufs[k]
             m_ = stage_bufs[k].numel()
             mine = J[rank * m_: rank * m_ + Bsz].to(dev)
             gather_info["own_shard_intact"] = bool(torch.equal(mine, dJT))
-            if args.dump and rank == 0:
+            if want_J:
                 sizes_ = [ld.shard_bounds(Bglobal, r_, world) for r_ in range(world)]
-                np.save(args.dump, torch.cat([J[r_ * m_: r_ * m_ + (hi_ - lo_)] for r_, (lo_, hi_) in enumerate(sizes_)]).cpu().numpy())
-    elif args.dump:
-        np.save(args.dump, dJT.cpu().numpy())
+                J_all = torch.cat([J[r_ * m_: r_ * m_ + (hi_ - lo_)] for r_, (lo_, hi_) in enumerate(sizes_)]).cpu().numpy()
+    elif want_J:
+        J_all = dJT.cpu().numpy()
+    if args.dump and rank == 0:
+        np.save(args.dump, J_all)
+    if args.dump_outputs and rank == 0:
+        # what the timed path handed back in its last step (before any --full leg reuses the buffers).  Rollout: J_T over the
+        # global batch, with status / iters when one process holds the whole batch; one-shot: this rank's u0, V_N, status, iters
+        if args.mode == "rollout":
+            outs = {"J_T": J_all} if distributed else {"J_T": J_all, "status": dst.cpu().numpy(), "iters": dit.cpu().numpy()}
+        else:
+            outs = {"u0": du0.cpu().numpy(), "V_N": dVN.cpu().numpy(), "status": dst.cpu().numpy(), "iters": dit.cpu().numpy()}
+        dump_outputs(args.dump_outputs, outs)
 
     # ---- roofline of the dominant kernel (the one launch per step), per launch, on rank 0's shard ----
     def roofline_of(kernel_ms, iters_mean, mode, qp_launch):
@@ -329,9 +374,9 @@ def main():
         roofline["mfma"] = {"achieved": round(mfma_insts * 2048 / (kernel_ms * 1e-3) / 1e12, 4), "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
                             "insts_per_launch": mfma_insts}
 
-    # ---- extra legs (N = 1 only): one-shot solves, the hard mix, the fused sweep, small-batch latency ----
+    # ---- extra legs (--full, N = 1 only): one-shot solves, the hard mix, the fused sweep, small-batch latency ----
     extra = {}
-    if world == 1 and not args.no_extras and args.mode == "rollout":
+    if args.full and world == 1 and not args.no_extras and args.mode == "rollout":
         dt1, kms1, v1 = run(launch_oneshot, max(args.steps, 20), 3, Bsz)
         it1, _ = totals()
         extra["oneshot"] = {"value": round(v1, 1), "unit": "QP-steps/s", "kernel_ms_per_launch": round(kms1, 4),
@@ -520,9 +565,9 @@ def main():
                                     "sync (what LQ_MPC_Controller.solve costs per call at m = 1); solve_batch_dev: back-to-back "
                                     "launches on resident data, HIP events"}
 
-    # ---- CPU baseline: the oracle (port) at 1 thread, --cpu-threads and all host cores; bounded samples; rank 0 at N=1 only ----
+    # ---- CPU baseline (--full): the oracle (port) at 1 thread, --cpu-threads and all host cores; bounded samples; rank 0 at N=1 only ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as orc
         native = orc.use_native_build()                    # gcc -O3 -march=native on THIS host (falls back to the shipped x86-64-v3 build)
         avail = len(os.sched_getaffinity(0))

@@ -23,6 +23,8 @@ DIST_JOBS = {
     "nccl_world1_final": ["--force-dist", "--config", "3", "--bsz", str(TWO_RANK["bsz"])],
     "nccl_world1_per_step": ["--force-dist", "--gather", "per-step", "--config", "3", "--bsz", str(TWO_RANK["bsz"])],
     "nccl_world1_c4": ["--force-dist", "--config", "4", "--bsz", "4096"],
+    # the plain single-process run (no collective)
+    "plain": ["--config", "3", "--bsz", str(TWO_RANK["bsz"])],
 }
 
 
@@ -48,8 +50,8 @@ def pytest_collection_modifyitems(config, items):
     tmp = tempfile.mkdtemp(prefix="lqmpc_dist_")
     jobs, script = {}, []
     for name, extra in DIST_JOBS.items():
-        f = {k: os.path.join(tmp, f"{name}.{k}") for k in ("out", "err", "npy", "rc")}
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + extra + _COMMON + ["--dump", f["npy"]]
+        f = {k: os.path.join(tmp, f"{name}.{k}") for k in ("out", "err", "npy", "rc", "outputs")}
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + extra + _COMMON + ["--dump", f["npy"], "--dump-outputs", f["outputs"]]
         script.append(" ".join(cmd) + f" > {f['out']} 2> {f['err']}; echo $? > {f['rc']}")
         jobs[name] = dict(cmd=cmd, **f)
     proc = subprocess.Popen(["bash", "-c", "\n".join(script)], cwd=ROOT, start_new_session=True,
@@ -68,7 +70,7 @@ def pytest_unconfigure(config):
 
 @pytest.fixture(scope="session")
 def dist_jobs(request):
-    """Waits for the bench.py jobs (if this run started any) and returns {name: {cmd, out, err, npy, rc}}."""
+    """Waits for the bench.py jobs (if this run started any) and returns {name: {cmd, out, err, npy, rc, outputs}}."""
     job = request.config._lqmpc_dist
     if job is None:
         return None

@@ -9,6 +9,7 @@ tests/conftest.py starts these jobs before anything in the test process touches 
 Every gathered curve must equal the single-process HIP result bit for bit (no result depends on which instances share a launch)
 and the CPU oracle to 1e-8."""
 import json
+import os
 
 import numpy as np
 import pytest
@@ -69,3 +70,22 @@ def test_rccl_branch_world_of_one(dist_jobs, solver, name, mode, cfg, bsz):
     assert np.array_equal(J, g["J_T"])
     ref = orc.rollout_batch(b["T"], *a)["J_T"]
     assert np.max(np.abs(J - ref) / np.abs(ref)) < 1e-8
+
+
+def test_plain_run_line_and_dumped_outputs(dist_jobs, solver):
+    """A plain bench.py run (no --full): the headline keys, none of the --full legs, and --dump-outputs holding what the timed
+    rollouts computed in their last step -- the single-process HIP result bit for bit, the CPU oracle to 1e-8."""
+    out, J = _job(dist_jobs, "plain")
+    bsz = TWO_RANK["bsz"]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(out)
+    assert out["steps"] == TWO_RANK["steps"] and out["warmup"] == TWO_RANK["warmup"] and out["ms_per_step"] > 0
+    assert out["value"] > 0 and out["dtype"] == "f64" and out["higher_is_better"] is True and "gather" not in out
+    assert out["cpu_baseline"] is None and not {"oneshot", "rollout_hard", "sweep", "bounds", "pcie", "latency"} & set(out)
+    d = dist_jobs["plain"]["outputs"]
+    got = {k: np.load(os.path.join(d, f"{k}.npy")) for k in ("J_T", "status", "iters")}
+    assert all(a.dtype == np.float64 and a.shape == (bsz,) for a in got.values())
+    assert np.array_equal(got["J_T"], J)
+    b, a, g = _single_process(solver, TWO_RANK["config"], bsz)
+    assert np.array_equal(got["J_T"], g["J_T"]) and np.all(got["status"] == 0) and np.all(got["iters"] >= 0)
+    ref = orc.rollout_batch(b["T"], *a)["J_T"]
+    assert np.max(np.abs(got["J_T"] - ref) / np.abs(ref)) < 1e-8
