@@ -33,6 +33,18 @@
  *     x0s (nx,K): the K initial states of lqmpc_max_vn_batch
  * All floating point is IEEE fp64, as in the reference.
  *
+ * Box limit: every kernel writes the box as u = v + c, |v| <= h (c = (lb+ub)/2, h = (ub-lb)/2), and scales its
+ * stopping tests with the gradient of the shifted problem, which holds P c.  A centre far from the inputs' own
+ * scale therefore costs accuracy in proportion to |c| (a one-sided limit written as [0, 1e6] is off by O(1)).  The
+ * calls refuse, with LQMPC_ERR_BAD_ARG, a box whose centre has |lb_k + ub_k| / 2 > LQMPC_MAX_BOX_CENTRE for any
+ * input k.  Symmetric boxes of any width (c = 0) are accepted; a one-sided limit is written with a finite other
+ * side near the largest input expected (e.g. [0, 2 u_max] instead of [0, 1e6]).
+ * Known inaccuracy inside the limit: with a one-sided box [0, b] and small states, many rows sit on or near the bound
+ * with multipliers far below |P c|.  The generic kernel and the workgroup kernel's interior-point fall-back (taken when its
+ * active-set solve cycles) then stop on the wrong face: relative errors up to 1e-7 measured at n = 120, 125 with the
+ * default eps (1e-12); the packed kernel's interior-point path (warm_start = 0) shows 1e-8 at n = 40.  eps = 1e-14
+ * reduces them (1e-14 at n = 125).  With default options the 16-lane-row kernels meet 1e-11 there (n = 20, 40).
+ *
  * Two flavours of every batched call:
  *   lqmpc_*_batch      per-instance pointers are HOST memory; the call copies in, runs, copies
  *                      out and returns when the results are in the caller's buffers.
@@ -60,9 +72,11 @@ extern "C" {
 
 typedef struct lqmpc_handle lqmpc_handle;
 
+#define LQMPC_MAX_BOX_CENTRE 1.0   /* largest |lb_k + ub_k| / 2 the solve / rollout / max-V_N / sweep calls accept */
+
 enum lqmpc_error {
     LQMPC_OK = 0,
-    LQMPC_ERR_BAD_ARG = -1,      /* NULL pointer, non-positive size, empty box, dims over the limits */
+    LQMPC_ERR_BAD_ARG = -1,      /* NULL pointer, non-positive size, empty box, box centre over the limit, dims over the limits */
     LQMPC_ERR_HIP = -2,          /* a HIP runtime call failed (message in lqmpc_last_error) */
     LQMPC_ERR_NO_DEVICE = -3,    /* no usable GPU */
     LQMPC_ERR_ALLOC = -4,        /* device or host allocation failed */

@@ -401,6 +401,15 @@ static int prepare(lqmpc_handle *h, const Call &c, KParams &p)
     for (int k = 0; k < c.nu; ++k)
         if (!(c.ub[k] > c.lb[k]) || !std::isfinite(c.lb[k]) || !std::isfinite(c.ub[k]))
             return fail(LQMPC_ERR_BAD_ARG, "every input needs a finite box with lb < ub");
+    // the kernels shift the box to its centre (u = v + c): a centre far out makes the answer inaccurate (include/lqmpc.h, "Box limit")
+    for (int k = 0; k < c.nu; ++k)
+        if (!(std::fabs(0.5 * c.lb[k] + 0.5 * c.ub[k]) <= LQMPC_MAX_BOX_CENTRE)) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "box of input %d is centred at %.17g: |lb + ub| / 2 must be <= %g (LQMPC_MAX_BOX_CENTRE); write a "
+                     "one-sided limit with a finite other side near the largest input expected", k, 0.5 * c.lb[k] + 0.5 * c.ub[k],
+                     (double)LQMPC_MAX_BOX_CENTRE);
+            return fail(LQMPC_ERR_BAD_ARG, buf);
+        }
     HIP_TRY(hipSetDevice(h->device));
     const int nx = c.nx, nu = c.nu, N = c.N;
     std::vector<double> sh;

@@ -100,13 +100,26 @@ class LQ_RDP_Behavior_Multiple:
 
     def _pool(self, k):
         """k handles (own stream each) for the concurrent passes of data_generation: the reference's six passes (error levels, five
-        horizons) are independent, and each is latency-bound on its own (a few hundred instances)."""
+        horizons) are independent, and each is latency-bound on its own (a few hundred instances).  Every call copies the
+        caller's solver options onto them, so the concurrent passes compute what the sequential ones would."""
         if not hasattr(self, "_handles"):
             self._handles = []
         from .mpc import BatchSolver
+        s = self._s()
         while len(self._handles) < k:
-            self._handles.append(BatchSolver(self._s().device))
+            self._handles.append(BatchSolver(s.device))
+        opts = {key: v for key, v in s.get_options().items() if key not in ("struct_size", "reserved", "reserved2")}
+        for hd in self._handles[:k]:
+            hd.set_options(**opts)
         return self._handles[:k]
+
+    def close(self):
+        """Shut the thread pool and destroy the pool handles of the concurrent passes (the caller's solver stays open)."""
+        ex = self.__dict__.pop("_executor", None)
+        if ex is not None:
+            ex.shutdown(wait=True)
+        for hd in self.__dict__.pop("_handles", []):
+            hd.close()
 
     def data_generation(self, N_points, ext_radius_max, info_ref, p=None, save_path=None, concurrent=True):
         """utils_class.py:766-959.  concurrent: the error-level pass and the five horizon passes (one fused sweep launch + one
