@@ -272,6 +272,50 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
                            double *dK, double *dalpha, double *dbeta, double *dxi, double *deta, double *dbound, double *deps,
                            double *daux, int32_t *dstatus);
 
+/* ---- prepared batch controller: set up once, then one box QP per instance and call at a measured state ----
+ * Every entry point above rebuilds the per-instance set-up (Riccati sweep, W = P^-1, the gain G of the unconstrained minimiser, P) in
+ * every call, although only the state changes between the steps of a closed loop the caller owns.  A controller does that work once
+ * and keeps it in HBM: one record per instance, [A | B | G | v_r | W | P] with W and P as packed lower triangles, padded to 256
+ * bytes.  A step reads [A | B | G | v_r], forms v = G x + v_r and tests it against the box; W is read only by the instances that
+ * have to iterate, P only when an iteration takes the primal side.  The active set a step ends on warm-starts the next step: shifted
+ * by one stage, as in lqmpc_rollout_batch, when the new state is nearer to the model's prediction A x + B u_0 than to the previous
+ * state x; as it is when the state did not advance (the same state asked again).  It never decides the answer.
+ *
+ * The controller takes a snapshot of the handle's options when it is created (eps, max_iter, r16_maxit, presolve, warm_start,
+ * kernel, layout, jit) and uses the handle's device, stream and scratch; later lqmpc_set_options calls do not reach it.  The record
+ * kernels serve exactly the shapes and options for which lqmpc_solve_batch runs the 16-lane-row family (prebuilt or run-time
+ * compiled); everywhere else the controller keeps device copies of A and B and every step is lqmpc_solve_batch_dev on them, so the
+ * interface covers the library's whole domain.  Destroy every controller BEFORE its handle.  Not thread-safe (as the handle).
+ *
+ * create: A, B per instance (instance-minor; host for _create, device for _create_dev), Q, R, P, lb, ub, x_ref, u_ref HOST (the
+ *   references may be NULL).  Same argument checks and error codes as lqmpc_solve_batch.  Everything is copied: the caller may free
+ *   or overwrite its arrays when the call returns (it waits for the stream).
+ * step: x is nx x Bsz, instance-minor; u0 (nu x Bsz), VN, status, iters as lqmpc_solve_batch returns them; VN, status, iters may be
+ *   NULL.  _dev: device pointers, enqueued on the handle's stream, returns at once.  A non-finite state gives status 2 for that
+ *   instance and leaves no trace in the controller.  A step sets the handle's lqmpc_last_kernel.
+ * reset: forget the stored active sets (the next step starts cold).  bytes: HBM held by the controller.  kernel: the kernel its
+ *   steps launch (contains "ctl"), or for a pass-through controller the kernel its last step ran.  destroy: NULL is fine.
+ * lqmpc_jit_compile_controller: the two kernels (factor, step) of a shape without prebuilt ones, compiled (or found in the cache
+ *   directory) now; needs no GPU; returns 2 or a negative lqmpc_error. */
+typedef struct lqmpc_controller lqmpc_controller;
+int lqmpc_controller_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                            const double *A, const double *B,
+                            const double *Q, const double *R, const double *P,
+                            const double *lb, const double *ub,
+                            const double *x_ref, const double *u_ref, lqmpc_controller **out);
+int lqmpc_controller_create_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                                const double *dA, const double *dB,
+                                const double *Q, const double *R, const double *P,
+                                const double *lb, const double *ub,
+                                const double *x_ref, const double *u_ref, lqmpc_controller **out);
+int lqmpc_controller_step(lqmpc_controller *c, const double *x, double *u0, double *VN, int32_t *status, int32_t *iters);
+int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, int32_t *dstatus, int32_t *diters);
+int lqmpc_controller_reset(lqmpc_controller *c);
+int64_t lqmpc_controller_bytes(const lqmpc_controller *c);
+const char *lqmpc_controller_kernel(const lqmpc_controller *c);
+int lqmpc_controller_destroy(lqmpc_controller *c);
+int lqmpc_jit_compile_controller(int nx, int nu, int N, char *log, int log_len);
+
 /* ---- timing on the handle's stream (hipEvents), for bench.py's roofline ----
  * begin/end bracket any number of *_dev calls; end waits for the stream and returns the
  * elapsed milliseconds between the two events. */

@@ -29,6 +29,9 @@ EXPORTS = [
     "lqmpc_bounds_batch", "lqmpc_bounds_batch_dev",
     "lqmpc_timer_begin", "lqmpc_timer_end",
     "lqmpc_jit_cache_dir", "lqmpc_jit_compile", "lqmpc_jit_compile_bounds",
+    "lqmpc_controller_create", "lqmpc_controller_create_dev", "lqmpc_controller_step", "lqmpc_controller_step_dev",
+    "lqmpc_controller_reset", "lqmpc_controller_bytes", "lqmpc_controller_kernel", "lqmpc_controller_destroy",
+    "lqmpc_jit_compile_controller",
 ]
 
 
@@ -103,6 +106,18 @@ def lib():
     L.lqmpc_jit_cache_dir.argtypes = [ctypes.c_char_p]
     L.lqmpc_jit_compile.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
     L.lqmpc_jit_compile_bounds.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    L.lqmpc_jit_compile_controller.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    ctl_create_args = dims + [P] * 9 + [ctypes.POINTER(_H)]
+    L.lqmpc_controller_create.argtypes = ctl_create_args
+    L.lqmpc_controller_create_dev.argtypes = ctl_create_args
+    L.lqmpc_controller_step.argtypes = [_H] + [P] * 5
+    L.lqmpc_controller_step_dev.argtypes = [_H] + [P] * 5
+    L.lqmpc_controller_reset.argtypes = [_H]
+    L.lqmpc_controller_bytes.argtypes = [_H]
+    L.lqmpc_controller_bytes.restype = ctypes.c_int64
+    L.lqmpc_controller_kernel.argtypes = [_H]
+    L.lqmpc_controller_kernel.restype = ctypes.c_char_p
+    L.lqmpc_controller_destroy.argtypes = [_H]
     # code objects of run-time compiled shapes are kept next to the library (falls back to memory only if not writable)
     L.lqmpc_jit_cache_dir(JIT_CACHE.encode())
     _lib = L
@@ -124,6 +139,15 @@ def jit_compile_bounds(nx, nu, N):
     rc = lib().lqmpc_jit_compile_bounds(int(nx), int(nu), int(N), log, len(log))
     if rc < 0:
         raise LqmpcError(f"lqmpc_jit_compile_bounds({nx},{nu},{N}) -> {rc}: {log.value.decode(errors='replace')}")
+    return rc
+
+
+def jit_compile_controller(nx, nu, N):
+    """The factor and step kernels of a prepared controller for one shape, compiled (or found in the cache) now; needs no GPU."""
+    log = ctypes.create_string_buffer(4096)
+    rc = lib().lqmpc_jit_compile_controller(int(nx), int(nu), int(N), log, len(log))
+    if rc < 0:
+        raise LqmpcError(f"lqmpc_jit_compile_controller({nx},{nu},{N}) -> {rc}: {log.value.decode(errors='replace')}")
     return rc
 
 

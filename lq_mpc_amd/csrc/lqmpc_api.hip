@@ -35,6 +35,9 @@ bool launch_jit(int device, const KParams &p, hipStream_t stream, const char **n
 bool launch_jit_bounds(int device, const BoundsParams &p, hipStream_t stream, std::string *why);
 // lqmpc_generic.hip: the generic kernel over a device-side list (p.perm, p.count_dev) with `cols` workspace columns
 void launch_generic_list(const KParams &p, int cols, hipStream_t stream);
+// lqmpc_ctl.hip: the factor / step kernels of a prepared controller (p.mode = MODE_CTL_FACTOR / MODE_CTL_STEP), prebuilt shapes
+bool ctl_available(int nx, int nu, int N);
+bool launch_ctl(const KParams &p, hipStream_t stream, const char **name);
 }  // namespace lqmpc
 
 using lqmpc::KParams;
@@ -1130,6 +1133,232 @@ int lqmpc_timer_end(lqmpc_handle *h, float *ms)
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     HIP_TRY(hipEventSynchronize(h->ev1));
     HIP_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
+    return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Prepared controllers: the per-instance set-up kept in HBM, one QP per instance and call from it (kernels: lqmpc_ctl.hip).
+struct lqmpc_controller {
+    lqmpc_handle *h = nullptr;
+    lqmpc_options opt;                        // the handle's options when the controller was made: every step runs under these
+    int nx = 0, nu = 0, N = 0;
+    int64_t Bsz = 0;
+    std::vector<double> Q, R, P, lb, ub, xref, uref;
+    bool has_xref = false, has_uref = false;
+    void *A = nullptr, *B = nullptr;          // the controller's copies (instance-minor): the hand-back and the pass-through read them
+    void *rec = nullptr, *face = nullptr;     // fast path: records (CtlRec); per instance the previous face, its state, the expected next state
+    void *vn = nullptr;                       // V_N of a step whose caller passed NULL (the solve kernels always write it); on first need
+    size_t bytes = 0;
+    bool fast = false, jit = false;           // fast: the record kernels serve the shape (jit: compiled at run time); else pass-through
+    std::string name = "lqmpc_solve_batch_dev";
+};
+
+namespace {
+
+void ctl_free(lqmpc_controller *c)
+{
+    for (void *q : {c->A, c->B, c->rec, c->face, c->vn}) if (q) (void)hipFree(q);
+    delete c;
+}
+
+int ctl_alloc(lqmpc_controller *c, void **q, size_t bytes)
+{
+    const hipError_t e = hipMalloc(q, bytes);
+    if (e != hipSuccess) { *q = nullptr; return fail(LQMPC_ERR_ALLOC, std::string("hipMalloc (controller): ") + hipGetErrorString(e)); }
+    c->bytes += bytes;
+    return 0;
+}
+
+Call ctl_call(const lqmpc_controller *c)
+{
+    return Call{c->nx, c->nu, c->N, 0, 0, lqmpc::MODE_SOLVE, 0, c->Bsz, c->Q.data(), c->R.data(), c->P.data(), c->lb.data(), c->ub.data(),
+                c->has_xref ? c->xref.data() : nullptr, c->has_uref ? c->uref.data() : nullptr, nullptr, nullptr, nullptr};
+}
+
+// the handle under the controller's options for the length of one call
+struct OptScope {
+    lqmpc_handle *h;
+    lqmpc_options saved;
+    OptScope(lqmpc_handle *h_, const lqmpc_options &o) : h(h_), saved(h_->opt) { h->opt = o; }
+    ~OptScope() { h->opt = saved; }
+};
+
+int ctl_launch(lqmpc_controller *c, const KParams &p)
+{
+    lqmpc_handle *h = c->h;
+    if (c->jit) {
+        std::string why;
+        if (!lqmpc::launch_jit(h->device, p, h->stream, nullptr, &why)) return fail(LQMPC_ERR_HIP, "run-time compiled controller kernel: " + why);
+    } else if (!lqmpc::launch_ctl(p, h->stream, nullptr)) return fail(LQMPC_ERR_UNSUPPORTED, "controller kernel launch failed");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+void ctl_bind(const lqmpc_controller *c, KParams &p)
+{
+    p.A = (const double *)c->A; p.B = (const double *)c->B;
+    p.ctl_rec = (double *)c->rec;
+    p.ctl_stride = lqmpc::ctl_rec_layout(c->nx, c->nu, c->N).stride;
+    p.ctl_face = (unsigned long long *)c->face;
+}
+
+int ctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B, hipMemcpyKind kind, const double *Q,
+               const double *R, const double *P, const double *lb, const double *ub, const double *x_ref, const double *u_ref,
+               lqmpc_controller **out)
+{
+    if (out) *out = nullptr;
+    if (!h || !out || !A || !B) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    // the argument checks, the shared block and the routing decisions of an ordinary solve on this handle
+    Call c0{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
+    KParams p;
+    int rc = prepare(h, c0, p);
+    if (rc) return rc;
+    lqmpc_controller *c = new lqmpc_controller();
+    c->h = h; c->opt = h->opt; c->nx = nx; c->nu = nu; c->N = N; c->Bsz = Bsz;
+    c->Q.assign(Q, Q + nx * nx); c->R.assign(R, R + nu * nu); c->P.assign(P, P + nx * nx);
+    c->lb.assign(lb, lb + nu); c->ub.assign(ub, ub + nu);
+    if (x_ref) { c->xref.assign(x_ref, x_ref + nx * N); c->has_xref = true; }
+    if (u_ref) { c->uref.assign(u_ref, u_ref + nu * N); c->has_uref = true; }
+    // fast path: exactly where lqmpc_solve_batch_dev runs the 16-lane-row family under these options
+    const bool r16 = use_spec(h, nx, nu, N) && use_r16(h, p, Bsz, INT32_MAX);
+    if (r16 || h->use_jit) {
+        if (r16 && lqmpc::ctl_available(nx, nu, N)) c->fast = true;
+        else if (h->opt.jit != 0) {
+            std::string why;
+            c->fast = c->jit = lqmpc::jit_available(h->device, nx, nu, N, lqmpc::MODE_CTL_FACTOR, &why) &&
+                               lqmpc::jit_available(h->device, nx, nu, N, lqmpc::MODE_CTL_STEP, &why);
+            if (!c->fast) g_err = "run-time compile unavailable, the controller passes through to lqmpc_solve_batch_dev: " + why;
+        }
+    }
+    const size_t b = (size_t)Bsz, nA = b * nx * nx * sizeof(double), nB = b * nx * nu * sizeof(double);
+    rc = ctl_alloc(c, &c->A, nA);
+    if (!rc) rc = ctl_alloc(c, &c->B, nB);
+    if (!rc && c->fast) {
+        rc = ctl_alloc(c, &c->rec, b * (size_t)lqmpc::ctl_rec_layout(nx, nu, N).stride * sizeof(double));
+        if (!rc) rc = ctl_alloc(c, &c->face, b * (size_t)(2 + 2 * nx) * sizeof(unsigned long long));
+    }
+    if (rc) { ctl_free(c); return rc; }
+    hipError_t e = hipMemcpyAsync(c->A, A, nA, kind, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->B, B, nB, kind, h->stream);
+    if (e == hipSuccess && c->fast) e = hipMemsetAsync(c->face, 0, b * (size_t)(2 + 2 * nx) * sizeof(unsigned long long), h->stream);
+    if (e != hipSuccess) { ctl_free(c); return fail(LQMPC_ERR_HIP, std::string("controller copy: ") + hipGetErrorString(e)); }
+    if (c->fast) {
+        char nm[96];
+        snprintf(nm, sizeof nm, "lqmpc_ctl_r%d%s_kernel<%d,%d,%d>", N * nu <= 32 ? 16 : 64, c->jit ? "_jit" : "", nx, nu, N);
+        if (!c->jit && lqmpc::r16_lanes(nx, nu, N) == 64) snprintf(nm, sizeof nm, "lqmpc_ctl_r64_kernel<%d,%d,%d>", nx, nu, N);
+        c->name = nm;
+        ctl_bind(c, p);
+        p.mode = lqmpc::MODE_CTL_FACTOR;
+        rc = ctl_launch(c, p);
+        if (rc) { ctl_free(c); return rc; }
+    }
+    // the caller may overwrite A and B as soon as this returns
+    e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { ctl_free(c); return fail(LQMPC_ERR_HIP, std::string("controller set-up: ") + hipGetErrorString(e)); }
+    *out = c;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lqmpc_controller_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B, const double *Q,
+                            const double *R, const double *P, const double *lb, const double *ub, const double *x_ref,
+                            const double *u_ref, lqmpc_controller **out)
+{
+    return ctl_create(h, nx, nu, N, Bsz, A, B, hipMemcpyHostToDevice, Q, R, P, lb, ub, x_ref, u_ref, out);
+}
+
+int lqmpc_controller_create_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *dA, const double *dB, const double *Q,
+                                const double *R, const double *P, const double *lb, const double *ub, const double *x_ref,
+                                const double *u_ref, lqmpc_controller **out)
+{
+    return ctl_create(h, nx, nu, N, Bsz, dA, dB, hipMemcpyDeviceToDevice, Q, R, P, lb, ub, x_ref, u_ref, out);
+}
+
+int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, int32_t *dstatus, int32_t *diters)
+{
+    if (!c || !dx || !du0) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    OptScope scope(h, c->opt);
+    const Call cl = ctl_call(c);
+    if (!c->fast) {
+        // pass-through: the existing solve path, unchanged, on the controller's copies of A and B
+        if (!dVN && !c->vn) { int rc = ctl_alloc(c, &c->vn, (size_t)c->Bsz * sizeof(double)); if (rc) return rc; }
+        int rc = lqmpc_solve_batch_dev(h, c->nx, c->nu, c->N, c->Bsz, (const double *)c->A, (const double *)c->B, cl.Q, cl.R, cl.P, cl.lb, cl.ub,
+                                       dx, cl.x_ref, cl.u_ref, du0, dVN ? dVN : (double *)c->vn, dstatus, diters);
+        if (!rc) c->name = h->last_kernel;
+        return rc;
+    }
+    KParams p;
+    int rc = prepare(h, cl, p);
+    if (rc) return rc;
+    ctl_bind(c, p);
+    p.x0 = dx; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
+    rc = prepare_hand_back(h, p);
+    if (rc) return rc;
+    p.mode = lqmpc::MODE_CTL_STEP;
+    rc = ctl_launch(c, p);
+    if (rc) return rc;
+    // whatever did not settle within r16_maxit iterations (or arrived with a non-finite state): the existing kernels, from scratch, over
+    // the device-side list -- as launch_r16_with_hand_back does for a one-shot solve
+    KParams f = p;
+    f.mode = lqmpc::MODE_SOLVE;
+    f.perm = p.fail_list; f.count_dev = p.fail_count; f.fail_list = nullptr; f.fail_count = nullptr; f.nwide = 0;
+    if (!f.VN) {
+        if (!c->vn) { rc = ctl_alloc(c, &c->vn, (size_t)c->Bsz * sizeof(double)); if (rc) return rc; }
+        f.VN = (double *)c->vn;
+    }
+    if (h->use_jit) lqmpc::launch_generic_list(f, JIT_FALLBACK_COLS, h->stream);
+    else if (!lqmpc::launch_spec(f, h->stream, nullptr)) return fail(LQMPC_ERR_UNSUPPORTED, "hand-back launch failed");
+    HIP_TRY(hipGetLastError());
+    h->last_kernel = c->name.c_str();
+    return 0;
+}
+
+int lqmpc_controller_step(lqmpc_controller *c, const double *x, double *u0, double *VN, int32_t *status, int32_t *iters)
+{
+    if (!c || !x || !u0) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)c->Bsz;
+    s.begin(b * 8 * (size_t)(c->nx + c->nu + 2));
+    const double *dx = s.in(x, b * c->nx);
+    double *du0 = s.out(u0, b * c->nu), *dVN = s.out(VN, b);
+    int32_t *dst = s.out(status, b), *dit = s.out(iters, b);
+    s.upload();
+    if (s.rc) return s.rc;
+    int rc = lqmpc_controller_step_dev(c, dx, du0, dVN, dst, dit);
+    if (rc) return rc;
+    s.back(u0, du0, b * c->nu); s.back(VN, dVN, b); s.back(status, dst, b); s.back(iters, dit, b);
+    return s.finish();
+}
+
+int lqmpc_controller_reset(lqmpc_controller *c)
+{
+    if (!c) return fail(LQMPC_ERR_BAD_ARG, "controller is NULL");
+    if (!c->face) return 0;
+    HIP_TRY(hipSetDevice(c->h->device));
+    HIP_TRY(hipMemsetAsync(c->face, 0, (size_t)c->Bsz * (size_t)(2 + 2 * c->nx) * sizeof(unsigned long long), c->h->stream));
+    return 0;
+}
+
+int64_t lqmpc_controller_bytes(const lqmpc_controller *c) { return c ? (int64_t)c->bytes : 0; }
+
+const char *lqmpc_controller_kernel(const lqmpc_controller *c) { return c ? c->name.c_str() : "none"; }
+
+int lqmpc_controller_destroy(lqmpc_controller *c)
+{
+    if (!c) return 0;
+    (void)hipSetDevice(c->h->device);
+    (void)hipStreamSynchronize(c->h->stream);
+    if (c->h->last_kernel == c->name.c_str()) c->h->last_kernel = "none";
+    ctl_free(c);
     return 0;
 }
 

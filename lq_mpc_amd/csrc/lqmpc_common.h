@@ -19,7 +19,9 @@ __device__ __forceinline__ void sfor(F &&f)
     if constexpr (I0 < I1) { f(ic<I0>{}); sfor<I0 + 1, I1>(f); }
 }
 
-enum Mode : int { MODE_SOLVE = 0, MODE_ROLLOUT = 1, MODE_MAXVN = 2, MODE_PROBE = 3, MODE_SWEEP = 4 /* max V_N, then the rollout */ };
+enum Mode : int { MODE_SOLVE = 0, MODE_ROLLOUT = 1, MODE_MAXVN = 2, MODE_PROBE = 3, MODE_SWEEP = 4 /* max V_N, then the rollout */,
+                  // the prepared controller (lqmpc_ctl.hip): the set-up written to one record per instance; one QP per instance from its record
+                  MODE_CTL_FACTOR = 5, MODE_CTL_STEP = 6 };
 
 // Offsets (in doubles) into the small "shared" device block that holds the data common to the
 // whole batch: Q, R, P, lb, ub, x_ref (nx,N), u_ref (nu,N), A_true, B_true, x0s (nx,K).
@@ -56,6 +58,27 @@ struct KParams {
     const int *count_dev;                 // packed kernel as the fallback pass: number of slots to process, on the device
     int r16_maxit;                        // active-set iteration cap of the 16-lane-row layout before it hands an instance back
     int r16_build;                        // options.r16_build: -1 auto, 0 throughput build, 1 latency build
+    double *ctl_rec;                      // MODE_CTL_*: the controller's records, instance-major (layout: CtlRec below)
+    long long ctl_stride;                 // ... doubles from one record to the next
+    unsigned long long *ctl_face;         // MODE_CTL_STEP, per instance (2 + 2 nx words): the active set of the previous step (lower, upper; 0 = none),
+                                          // the state it was found at, the state the model expected next
+};
+
+// One record of a prepared controller, in doubles: [A | B | G | v_r] (what every step reads) then [W] then [P] (what only the active-set
+// iterations read), W and P as packed lower triangles.  The stride is padded to 256 bytes.
+struct CtlRec {
+    int oA, oB, oG, oV, oW, oP, tri, stride;
+};
+__host__ __device__ constexpr CtlRec ctl_rec_layout(int nx, int nu, int N)
+{
+    const int n = N * nu, tri = n * (n + 1) / 2;
+    const int oB = nx * nx, oG = oB + nx * nu, oV = oG + n * nx, oW = oV + n, oP = oW + tri;
+    return CtlRec{0, oB, oG, oV, oW, oP, tri, (oP + tri + 31) / 32 * 32};
+}
+template <int NX, int NU, int N>
+struct CtlRecT {
+    static constexpr CtlRec L = ctl_rec_layout(NX, NU, N);
+    static constexpr int oA = L.oA, oB = L.oB, oG = L.oG, oV = L.oV, oW = L.oW, oP = L.oP, tri = L.tri, stride = L.stride;
 };
 
 constexpr int ORDER_BUCKETS = 512;           // difficulty buckets of the ordering: 16 per binade of the key over [2^-2, 2^30)

@@ -1,0 +1,74 @@
+// lqmpc_ctl.hip -- the two kernels of a prepared controller (lqmpc_controller_*, include/lqmpc.h) in the 16-lane-row layout.
+//
+// A one-shot solve spends about half of its launch on what does not depend on the state: the backward Riccati sweep, W = P^-1, the
+// gain G of the unconstrained minimiser and P.  A controller runs that once (MODE_CTL_FACTOR: the set-up of lqmpc_r16_body.h as it
+// stands, then one record per instance written to HBM instead of a QP) and every step after it (MODE_CTL_STEP) starts from the record:
+//   [A | B | G | v_r]   read by every step: v = G x + v_r, the test against the box, the model for V_N
+//   [W]                 packed lower triangle, brought into LDS only by the instances of a wavefront that have to iterate
+//   [P]                 packed lower triangle, only when an iteration takes the primal side (|A| > n / 2)
+// Records are instance-major and padded to 256 bytes, so the lanes of an instance read consecutive addresses.  The iterations are the
+// qp() of lqmpc_r16_body.h, not a copy; the face a step ends on is kept per instance (two 64-bit masks, with the state it was found at
+// and the state the model expected next) and warm-starts the next one: shifted by one stage as the rollout shifts it when the state
+// advanced, unshifted when it stayed.
+#include "lqmpc_r16_body.h"
+
+namespace lqmpc {
+
+// register / LDS budget: as the one-shot kernels of the same shape (R16Build in lqmpc_r16.hip)
+template <int NX, int NU, int N, int LPI>
+struct CtlBuild {
+    static constexpr int OCC = ((LPI == 16 && N * NU > 10) || LPI == 64) ? 2 : 1;
+    static constexpr long long LDS_BYTES = (long long)(64 / LPI) * R16<NX, NU, N, LPI, (OCC == 2)>::INST * 8;
+    static constexpr int WAVES = ((OCC == 2 || (N * NU <= 10 && LPI == 16)) && LDS_BYTES * 8 <= 160 * 1024) ? 2 : 1;
+};
+
+template <int NX, int NU, int N, int MODE, int LPI>
+__global__ void __launch_bounds__(64, (CtlBuild<NX, NU, N, LPI>::WAVES)) lqmpc_ctl_kernel(KParams p)
+{
+    using C = R16<NX, NU, N, LPI, (CtlBuild<NX, NU, N, LPI>::OCC == 2)>;
+    __shared__ double lds_raw[C::IPW * C::INST];
+    r16_body<NX, NU, N, MODE, LPI, CtlBuild<NX, NU, N, LPI>::OCC>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
+}
+
+struct CtlEntry {
+    int nx, nu, N, lpi;
+    const char *name;
+    void (*launch)(const KParams &, hipStream_t);
+};
+
+template <int NX, int NU, int N, int LPI>
+static void launch_ctl_one(const KParams &p, hipStream_t stream)
+{
+    constexpr int IPW = 64 / LPI;
+    const dim3 grid((unsigned)((p.Bsz + IPW - 1) / IPW));
+    if (p.mode == MODE_CTL_FACTOR) hipLaunchKernelGGL((lqmpc_ctl_kernel<NX, NU, N, MODE_CTL_FACTOR, LPI>), grid, dim3(64), 0, stream, p);
+    else hipLaunchKernelGGL((lqmpc_ctl_kernel<NX, NU, N, MODE_CTL_STEP, LPI>), grid, dim3(64), 0, stream, p);
+}
+
+// the prebuilt shapes; every other shape of the 16-lane-row domain is compiled at run time (lqmpc_jit.hip)
+static const CtlEntry g_ctl[] = {
+    {4, 2, 10, 16, "lqmpc_ctl_r16_kernel<4,2,10>", launch_ctl_one<4, 2, 10, 16>},
+    {2, 1, 10, 16, "lqmpc_ctl_r16_kernel<2,1,10>", launch_ctl_one<2, 1, 10, 16>},
+    {4, 2, 20, 64, "lqmpc_ctl_r64_kernel<4,2,20>", launch_ctl_one<4, 2, 20, 64>},
+};
+
+static const CtlEntry *find_ctl(int nx, int nu, int N)
+{
+    for (const CtlEntry &e : g_ctl)
+        if (e.nx == nx && e.nu == nu && e.N == N) return &e;
+    return nullptr;
+}
+
+bool ctl_available(int nx, int nu, int N) { return find_ctl(nx, nu, N) != nullptr; }
+
+// p.mode: MODE_CTL_FACTOR or MODE_CTL_STEP
+bool launch_ctl(const KParams &p, hipStream_t stream, const char **name)
+{
+    const CtlEntry *e = find_ctl(p.nx, p.nu, p.N);
+    if (!e || (p.mode != MODE_CTL_FACTOR && p.mode != MODE_CTL_STEP)) return false;
+    e->launch(p, stream);
+    if (name) *name = e->name;
+    return true;
+}
+
+}  // namespace lqmpc

@@ -235,7 +235,8 @@ static const std::vector<char> *get_code(int nx, int nu, int N, int mode, std::s
 static const char *mode_tag(int mode)
 {
     switch (mode) { case MODE_SOLVE: return "solve"; case MODE_ROLLOUT: return "rollout"; case MODE_MAXVN: return "maxvn";
-                    case MODE_PROBE: return "probe"; default: return "sweep"; }
+                    case MODE_PROBE: return "probe"; case MODE_CTL_FACTOR: return "controller factor"; case MODE_CTL_STEP: return "controller step";
+                    default: return "sweep"; }
 }
 
 // the kernel of (shape, mode) on `device`, ready to launch; nullptr (reason in err) when the shape is outside the domain or the
@@ -362,6 +363,22 @@ int lqmpc_jit_compile(int nx, int nu, int N, char *log, int log_len)
         }
     }
     return count;
+}
+
+// ... and the two kernels of a prepared controller (lqmpc_ctl.hip: factor, step) of a shape of the 16-lane-row domain; returns 2
+int lqmpc_jit_compile_controller(int nx, int nu, int N, char *log, int log_len)
+{
+    if (log && log_len > 0) log[0] = '\0';
+    if (!lqmpc::jit_r16_shape(nx, nu, N, nullptr)) return LQMPC_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lock(lqmpc::g_mu);
+    for (int mode : {(int)lqmpc::MODE_CTL_FACTOR, (int)lqmpc::MODE_CTL_STEP}) {
+        std::string err;
+        if (!lqmpc::get_code(nx, nu, N, mode, err)) {
+            if (log && log_len > 0) snprintf(log, (size_t)log_len, "%s: %s", lqmpc::mode_tag(mode), err.c_str());
+            return LQMPC_ERR_UNSUPPORTED;
+        }
+    }
+    return 2;
 }
 
 // ... and the pair of on-chip bound-coefficient kernels of a shape (nx <= 8, nu <= 4, LDS image within 160 KiB); returns 2

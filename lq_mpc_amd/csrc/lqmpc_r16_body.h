@@ -221,14 +221,27 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
     // first time an iteration needs it (C4 4.92 -> 4.58 ms).  Four instances per wavefront: in every set-up -- the mere presence of
     // the on-demand call in qp() costs every primal-side iteration of these kernels ~25 % (C3 hard mix 1.27 -> 1.56 ms, default mix
     // 0.338 -> 0.345 ms, measured with the call inside the iteration loop, outside it, and never taken).
-    constexpr bool LAZY_P = (LPI == 64);
+    // The controller's step (MODE_CTL_STEP) has no set-up at all: G and v_r come from the instance's record, W when an instance of the
+    // wavefront iterates, P when an iteration takes the primal side.  Its factor launch (MODE_CTL_FACTOR) always builds P.
+    constexpr bool CTL_F = MODE == MODE_CTL_FACTOR, CTL_S = MODE == MODE_CTL_STEP;
+    using CR = CtlRecT<NX, NU, N>;
+    constexpr bool LAZY_P = (LPI == 64 && !CTL_F) || CTL_S;
     bool P_ready = !LAZY_P;
+    bool W_ready = !CTL_S;
+    bool face_stays = false;                 // MODE_CTL_STEP: the state did not advance since the stored face was found (set before qp())
+    // row and column of element e of a packed lower triangle
+    auto tri_rc = [](int e, int &r, int &c) {
+        r = (int)((__builtin_sqrtf(8.0f * (float)e + 1.0f) - 1.0f) * 0.5f);
+        r = ((r + 1) * (r + 2) / 2 <= e) ? r + 1 : r;
+        r = (r * (r + 1) / 2 > e) ? r - 1 : r;
+        c = e - r * (r + 1) / 2;
+    };
     // the set-up's guess of the active set at x0 (lqmpc_r16_setup.h, ROLL): the face the first, cold-started QP begins from; the
     // stage gains are kept in registers through the sweep, so short horizons only, and where the first QP is the one at x0
 #ifdef LQMPC_NO_ROLL                         // (dev builds: tools/prof_build.sh)
     constexpr bool ROLL = false;
 #else
-    constexpr bool ROLL = LPI == 16 && N * ((NX + 3) / 4) <= 12 && MODE != MODE_MAXVN;
+    constexpr bool ROLL = LPI == 16 && N * ((NX + 3) / 4) <= 12 && MODE != MODE_MAXVN && !CTL_F && !CTL_S;
 #endif
     unsigned cold32[2] = {0u, 0u};
     bool cold_armed = false;                 // set by the caller of qp() for the QP at x0
@@ -238,7 +251,16 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
     long long prof_slowt = 0;
     long long prof_ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-    {
+    if constexpr (CTL_S) {
+        const double *rc = p.ctl_rec + b * p.ctl_stride;
+#pragma unroll
+        for (int s = 0; s < RB; ++s) {
+            const int mr = vrow[s] ? rw[s] : 0;
+#pragma unroll
+            for (int a = 0; a < NX; ++a) G[s][a] = rc[CR::oG + mr * NX + a];
+            vr[s] = vrow[s] ? rc[CR::oV + mr] : 0.0;
+        }
+    } else {
         // Set-up on the matrix core (lqmpc_r16_setup.h): Riccati recursion, W by rank-NU tile updates, G from the same sweep, P from
         // its Toeplitz form -- v_mfma_f64_4x4x4_4b_f64 products only.  MFMA block g = (lane >> 2) & 3 works for the instance of lanes
         // 16g .. 16g+15 (LPI = 16), so the set-up takes its inputs and its LDS by g and hands G back through LDS.
@@ -341,6 +363,47 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
         }
         RPROF(6);
     }
+    if constexpr (CTL_F) {
+        // the record of my instance: [A | B | G | v_r | W | P], the triangles element by element over the lanes of the instance
+        __syncthreads();
+        if (valid) {
+            double *rc = p.ctl_rec + b * p.ctl_stride;
+            for (int e = i; e < NX * NX; e += LPI) rc[CR::oA + e] = p.A[(long long)e * Bsz + b];
+            for (int e = i; e < NX * NU; e += LPI) rc[CR::oB + e] = p.B[(long long)e * Bsz + b];
+#pragma unroll
+            for (int s = 0; s < RB; ++s) {
+                if (vrow[s]) {
+#pragma unroll
+                    for (int a = 0; a < NX; ++a) rc[CR::oG + rw[s] * NX + a] = G[s][a];
+                    rc[CR::oV + rw[s]] = vr[s];
+                }
+            }
+            for (int e = i; e < CR::tri; e += LPI) {
+                int r, c;
+                tri_rc(e, r, c);
+                rc[CR::oW + e] = Wp[ad2(r, c)];
+                rc[CR::oP + e] = Pp[ad2(r, c)];
+            }
+        }
+        return;
+    }
+    // W or P of my instance from its record into LDS (the instances that iterate only: the others never use what they read there)
+    auto ctl_fill = [&](ldsd *M, int off, bool on) {
+        const double *src = p.ctl_rec + b * p.ctl_stride + off;
+        constexpr int CNT = (CR::tri + LPI - 1) / LPI;
+        double val[CNT];
+#pragma unroll
+        for (int k = 0; k < CNT; ++k) { const int e = i + LPI * k; val[k] = (on && e < CR::tri) ? src[e] : 0.0; }
+#pragma unroll
+        for (int k = 0; k < CNT; ++k) {
+            const int e = i + LPI * k;
+            if (on && e < CR::tri) {
+                if constexpr (PACKED) M[e] = val[k];
+                else { int r, c; tri_rc(e, r, c); M[r * LDW + c] = val[k]; M[c * LDW + r] = val[k]; }
+            }
+        }
+        __syncthreads();
+    };
     RPROF_START;
     RPROF_ADD(13, clock64() - prof_t0);
 
@@ -416,6 +479,9 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                 const mask_t top = nmask & ~(nmask >> NU);
                 mL = (pL >> NU) | (pL & top);
                 mU = (pU >> NU) | (pU & top);
+                if constexpr (CTL_S) {
+                    if (face_stays) { mL = pL; mU = pU; }         // ... unless the state stayed where that face is the optimum
+                }
             } else if (ROLL && cold_armed && (cold32[0] | cold32[1]) != 0u) {
                 mL = cold32[0]; mU = cold32[1];
             } else {
@@ -439,9 +505,13 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                 bg = p.perm ? (long long)p.perm[sl] : sl;
                 Lg = (ldsd *)lds_raw + gq * C::INST;
             }
-            r16_build_P<NX, NU, N, LPI, PACKED>(setup_args(p), bg, Lg, C::oP, C::oD);
+            if constexpr (CTL_S) ctl_fill(Pp, CR::oP, busy);
+            else r16_build_P<NX, NU, N, LPI, PACKED>(setup_args(p), bg, Lg, C::oP, C::oD);
             P_ready = true;
             need_P = false;
+        }
+        if constexpr (CTL_S) {
+            if (!W_ready && __ballot(busy) != 0ull) { ctl_fill(Wp, CR::oW, busy); W_ready = true; }
         }
         if (__ballot(busy) != 0ull) {
 #pragma unroll 1
@@ -981,11 +1051,15 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                 for (int a = 0; a < NX; ++a) {
 #pragma unroll
                     for (int c = 0; c < NX; ++c) {
-                        cA[a * NX + c] = p.rec ? p.rec[bq * REC + a * NX + c] : p.A[(long long)(a * NX + c) * Bsz + bq];
+                        if constexpr (CTL_S) cA[a * NX + c] = p.ctl_rec[bq * p.ctl_stride + CR::oA + a * NX + c];
+                        else cA[a * NX + c] = p.rec ? p.rec[bq * REC + a * NX + c] : p.A[(long long)(a * NX + c) * Bsz + bq];
                         cP[a * NX + c] = sh[p.so.P + a * NX + c];
                     }
 #pragma unroll
-                    for (int k = 0; k < NU; ++k) cB[a * NU + k] = p.rec ? p.rec[bq * REC + NX * NX + a * NU + k] : p.B[(long long)(a * NU + k) * Bsz + bq];
+                    for (int k = 0; k < NU; ++k) {
+                        if constexpr (CTL_S) cB[a * NU + k] = p.ctl_rec[bq * p.ctl_stride + CR::oB + a * NU + k];
+                        else cB[a * NU + k] = p.rec ? p.rec[bq * REC + NX * NX + a * NU + k] : p.B[(long long)(a * NU + k) * Bsz + bq];
+                    }
                 }
             }
             __syncthreads();
@@ -994,11 +1068,15 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
             for (int a = 0; a < NX; ++a) {
 #pragma unroll
                 for (int c = 0; c < NX; ++c) {
-                    Am[a][c] = p.rec ? p.rec[bq * REC + a * NX + c] : p.A[(long long)(a * NX + c) * Bsz + bq];
+                    if constexpr (CTL_S) Am[a][c] = p.ctl_rec[bq * p.ctl_stride + CR::oA + a * NX + c];
+                    else Am[a][c] = p.rec ? p.rec[bq * REC + a * NX + c] : p.A[(long long)(a * NX + c) * Bsz + bq];
                     Pm[a][c] = sh[p.so.P + a * NX + c];
                 }
 #pragma unroll
-                for (int k = 0; k < NU; ++k) Bmm[a][k] = p.rec ? p.rec[bq * REC + NX * NX + a * NU + k] : p.B[(long long)(a * NU + k) * Bsz + bq];
+                for (int k = 0; k < NU; ++k) {
+                    if constexpr (CTL_S) Bmm[a][k] = p.ctl_rec[bq * p.ctl_stride + CR::oB + a * NU + k];
+                    else Bmm[a][k] = p.rec ? p.rec[bq * REC + NX * NX + a * NU + k] : p.B[(long long)(a * NU + k) * Bsz + bq];
+                }
             }
         }
         auto Av = [&](int a, int c) -> double { if constexpr (OCC == 2) return cA[a * NX + c]; else return Am[a][c]; };
@@ -1049,7 +1127,48 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
             __syncthreads();
             return c;
         };
-        if (MODE == MODE_SOLVE) {
+        if constexpr (CTL_S) {
+            // one QP at the caller's state, warm-started from the face the previous step left (zero: none, or lqmpc_controller_reset)
+            double x[NX], v[RB], u[NU];
+#pragma unroll
+            for (int a = 0; a < NX; ++a) x[a] = p.x0[(long long)a * Bsz + bq];
+            // Stored per instance: the face the previous step ended on, the state x' it was found at and the state A x' + B u_0 the model
+            // expected next.  A state nearer to the expected one has advanced by a stage: the face is shifted, as in the rollout.  A state
+            // nearer to x' (the same state asked again, a plant that did not move) keeps the face as it is: it is the optimum there.
+            unsigned long long *fc = p.ctl_face + bq * (2 + 2 * NX);
+            pL = fc[0]; pU = fc[1];
+            {
+                double dprev = 0.0, dnext = 0.0;
+#pragma unroll
+                for (int a = 0; a < NX; ++a) {
+                    const double e0 = x[a] - __longlong_as_double((long long)fc[2 + a]);
+                    const double e1 = x[a] - __longlong_as_double((long long)fc[2 + NX + a]);
+                    dprev = __builtin_fma(e0, e0, dprev);
+                    dnext = __builtin_fma(e1, e1, dnext);
+                }
+                face_stays = dprev < dnext;
+            }
+            qp(x, v);
+            double vn = 0.0;
+            if (p.VN) vn = value_fn(x, v);
+            stage_input(v, 0, u);
+            if (writer) {
+                fc[0] = pL; fc[1] = pU;
+#pragma unroll
+                for (int a = 0; a < NX; ++a) {
+                    double xn = 0.0;
+#pragma unroll
+                    for (int cc = 0; cc < NX; ++cc) xn = __builtin_fma(Av(a, cc), x[cc], xn);
+#pragma unroll
+                    for (int k = 0; k < NU; ++k) xn = __builtin_fma(Bv(a, k), u[k], xn);
+                    fc[2 + a] = (unsigned long long)__double_as_longlong(x[a]);
+                    fc[2 + NX + a] = (unsigned long long)__double_as_longlong(xn);
+                }
+                if (p.VN) p.VN[b] = vn;
+#pragma unroll
+                for (int k = 0; k < NU; ++k) p.u0[(long long)k * Bsz + bq] = u[k];
+            }
+        } else if (MODE == MODE_SOLVE) {
             double x[NX], v[RB], u[NU];
 #pragma unroll
             for (int a = 0; a < NX; ++a) x[a] = p.rec ? p.rec[bq * REC + NX * NX + NX * NU + a] : p.x0[(long long)a * Bsz + bq];

@@ -7,7 +7,8 @@ Same class names, positional signatures and return dictionaries as
         -> {'X', 'U', 'J_T'}                                                              (lines 213-285)
 so callers written against the reference (LQ_RDP_Behavior*, mpc_test.py) run unchanged, plus the
 batched entry points a GPU needs (the reference API is one instance per call):
-    BatchSolver.solve_batch / rollout_batch / max_vn_batch  over instance-minor (SoA) arrays.
+    BatchSolver.solve_batch / rollout_batch / max_vn_batch  over instance-minor (SoA) arrays,
+    BatchController(solver, ...).step(x): the set-up kept on the GPU, one QP per instance and call.
 Everything executes in the HIP library behind include/lqmpc.h; there is no CPU path here.
 """
 import ctypes
@@ -284,6 +285,88 @@ class BatchSolver:
                                                   _ptr(de_A), _ptr(de_B), _ptr(dMV), _ptr(x), _ptr(p), float(V_expert),
                                                   _ptr(dK), _ptr(dalpha), _ptr(dbeta), _ptr(dxi), _ptr(deta), _ptr(dbound),
                                                   _ptr(deps), _ptr(daux), _ptr(dstatus)))
+
+
+class BatchController:
+    """A prepared controller for a batch (include/lqmpc.h, lqmpc_controller_*): the per-instance set-up is computed once and
+    kept in HBM, every step() solves one box QP per instance at the states it is given.  For closed loops the caller owns
+    (a simulator in torch, recorded data, hardware): the states come from outside, only u_0 comes from here.
+
+    A, B: numpy arrays (nx, nx, Bsz) / (nx, nu, Bsz) or device tensors of those shapes (anything with .shape and .data_ptr()).
+    The controller runs under the solver's options as they are NOW; it keeps the solver alive and must be closed before it."""
+
+    def __init__(self, solver, N, A, B, Q, R, P, lb, ub, x_ref=None, u_ref=None):
+        self._c = None
+        if not isinstance(solver, BatchSolver):
+            raise _lib.LqmpcError("BatchController needs a BatchSolver (one GPU, one stream)")
+        self._solver = solver
+        self._L = solver._L
+        on_device = hasattr(A, "data_ptr")
+        if on_device:
+            sa, sb = tuple(A.shape), tuple(B.shape)
+            if len(sa) != 3 or len(sb) != 3 or sa[0] != sa[1] or sb[0] != sa[0] or sb[2] != sa[2]:
+                raise ValueError("A must be (nx,nx,Bsz) and B (nx,nu,Bsz), instance-minor")
+            if not (A.is_contiguous() and B.is_contiguous()) or "float64" not in str(A.dtype) or "float64" not in str(B.dtype):
+                raise ValueError("device A and B must be contiguous float64")
+            nx, nu, Bsz = sa[0], sb[1], sa[2]
+        else:
+            A, B, nx, nu, Bsz = BatchSolver._dims(A, B)
+        self.N, self.nx, self.nu, self.Bsz = int(N), nx, nu, Bsz
+        Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
+        lb, ub = _f64(lb, (nu,)), _f64(ub, (nu,))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, self.N), _ref_or_none(u_ref, nu, self.N)
+        c = ctypes.c_void_p()
+        make = self._L.lqmpc_controller_create_dev if on_device else self._L.lqmpc_controller_create
+        _lib.check(make(solver._h, nx, nu, self.N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P), _ptr(lb), _ptr(ub),
+                        _ptr(x_ref), _ptr(u_ref), ctypes.byref(c)))
+        self._c = c
+
+    def _live(self):
+        if self._c is None or not self._c.value:
+            raise _lib.LqmpcError("the controller is closed")
+        return self._c
+
+    def step(self, x):
+        """One QP per instance at the states x (nx, Bsz), host arrays in and out."""
+        x = _f64(x, (self.nx, self.Bsz))
+        u0 = np.empty((self.nu, self.Bsz)); VN = np.empty(self.Bsz)
+        status = np.empty(self.Bsz, dtype=np.int32); iters = np.empty(self.Bsz, dtype=np.int32)
+        _lib.check(self._L.lqmpc_controller_step(self._live(), _ptr(x), _ptr(u0), _ptr(VN), _ptr(status), _ptr(iters)))
+        return {"u_0": u0, "V_N": VN, "status": status, "iters": iters}
+
+    def step_dev(self, dx, du0, dVN=None, dstatus=None, diters=None):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once."""
+        _lib.check(self._L.lqmpc_controller_step_dev(self._live(), _ptr(dx), _ptr(du0), _ptr(dVN), _ptr(dstatus), _ptr(diters)))
+
+    def reset(self):
+        """Forget the active sets carried from the previous step: the next step starts cold."""
+        _lib.check(self._L.lqmpc_controller_reset(self._live()))
+
+    @property
+    def kernel(self):
+        return self._L.lqmpc_controller_kernel(self._live()).decode()
+
+    @property
+    def nbytes(self):
+        return int(self._L.lqmpc_controller_bytes(self._live()))
+
+    def close(self):
+        if getattr(self, "_c", None) is not None and self._c.value:
+            if self._solver._h.value:                     # (a closed solver has taken its stream with it: nothing left to wait for)
+                self._L.lqmpc_controller_destroy(self._c)
+            self._c = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 _default_solver = None
