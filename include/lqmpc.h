@@ -122,7 +122,7 @@ typedef struct lqmpc_options {
                           optimum, otherwise the interior-point loop runs.  -1 auto (= presolve), 0 off, 1 on.
                           Specialised kernels only.  (default -1) */
     /* ---- layout / tuning selectors (the tests force every path through these; defaults are the measured best) ---- */
-    int32_t layout;     /* which specialised family serves a shape that has both: -1 auto (lqmpc_api.hip: use_r16), 0 the
+    int32_t layout;     /* which specialised family serves a shape that has both: -1 auto (lqmpc_api.hip: make_plan), 0 the
                           packed register-resident kernel (and its two-tier launch for sorted rollouts), 1 the 16-lane-row
                           kernel.  (default -1) */
     int32_t r16_maxit;  /* active-set iterations the 16-lane-row kernel spends on one QP before it hands the instance back to

@@ -1,9 +1,7 @@
 // lqmpc_api.hip -- host side of the C ABI declared in include/lqmpc.h: handle, argument checks,
 // shared-block packing, workspace management, kernel dispatch, host<->device staging.
-#include "lqmpc_common.h"
-#include "lqmpc_bounds.h"
+#include "lqmpc_launch.h"
 #include "../../include/lqmpc.h"
-
 
 #include <algorithm>
 #include <cmath>
@@ -12,33 +10,6 @@
 #include <cstring>
 #include <string>
 #include <vector>
-
-namespace lqmpc {
-long long generic_ws_entries(int nx, int nu, int N);
-void launch_generic(const KParams &p, hipStream_t stream);
-// lqmpc_spec.hip: returns false when no specialisation is built for (nx,nu,N)
-bool spec_available(int nx, int nu, int N);
-bool launch_spec(const KParams &p, hipStream_t stream, const char **name);
-void launch_order_scatter(const KParams &p, int *perm, hipStream_t stream);
-bool spec_tiered_available(int nx, int nu, int N);
-// lqmpc_r16.hip: rollouts with one instance per 16-lane row (n <= 32)
-bool r16_available(int nx, int nu, int N);
-int r16_lanes(int nx, int nu, int N);       // 16, 64 (one instance per wavefront: n > 32) or 0
-bool launch_r16(const KParams &p, hipStream_t stream, const char **name);
-// lqmpc_wg.hip: one instance per workgroup, 32 < n <= 128
-bool wg_supported(const KParams &p, const double *lb, const double *ub);
-bool launch_wg(const KParams &p, hipStream_t stream, const char **name);
-// lqmpc_jit.hip: the 16-lane-row kernel (and the probe) of a shape without a prebuilt instantiation, compiled at run time
-bool jit_r16_shape(int nx, int nu, int N, int *lpi);
-bool jit_available(int device, int nx, int nu, int N, int mode, std::string *why);
-bool launch_jit(int device, const KParams &p, hipStream_t stream, const char **name, std::string *why);
-bool launch_jit_bounds(int device, const BoundsParams &p, hipStream_t stream, std::string *why);
-// lqmpc_generic.hip: the generic kernel over a device-side list (p.perm, p.count_dev) with `cols` workspace columns
-void launch_generic_list(const KParams &p, int cols, hipStream_t stream);
-// lqmpc_ctl.hip: the factor / step kernels of a prepared controller (p.mode = MODE_CTL_FACTOR / MODE_CTL_STEP), prebuilt shapes
-bool ctl_available(int nx, int nu, int N);
-bool launch_ctl(const KParams &p, hipStream_t stream, const char **name);
-}  // namespace lqmpc
 
 using lqmpc::KParams;
 
@@ -89,8 +60,6 @@ struct lqmpc_handle {
     std::vector<double> shared_host; // last uploaded shared block
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const char *last_kernel = "none";
-    bool use_wg = false;             // set by prepare(): this call runs on the workgroup kernel
-    bool use_jit = false;            // set by prepare(): this call runs on a run-time compiled 16-lane-row kernel (lqmpc_jit.hip)
 };
 
 constexpr int JIT_FALLBACK_COLS = 1024;   // workspace columns of the generic kernel when it only serves a hand-back list
@@ -382,20 +351,121 @@ static bool host_first_gain(int nx, int nu, int N, const double *A, const double
     return true;
 }
 
-static bool use_spec(const lqmpc_handle *h, int nx, int nu, int N)
-{
-    return h->opt.kernel != LQMPC_KERNEL_GENERIC && h->opt.kernel != LQMPC_KERNEL_WORKGROUP && lqmpc::spec_available(nx, nu, N);
-}
-
 struct Call {
     int nx, nu, N, T, K, mode, true_per_instance;
     int64_t Bsz;
     const double *Q, *R, *P, *lb, *ub, *x_ref, *u_ref, *At_sh, *Bt_sh, *x0s;
 };
 
-// Pack the batch-shared data, upload it (skipped when identical to the last upload), size the
-// workspace, fill the kernel parameter block.
-static int prepare(lqmpc_handle *h, const Call &c, KParams &p)
+// references or an off-centre box: the linear term has a constant part
+static bool has_lin(const Call &c)
+{
+    bool lin = c.x_ref || c.u_ref;
+    for (int k = 0; k < c.nu; ++k) lin = lin || (c.ub[k] + c.lb[k] != 0.0);
+    return lin;
+}
+
+// Everything the host decides about one call before it enqueues anything (make_plan); the entry points, build_order, launch, the
+// hand-back pass and lqmpc_reserve only read it.
+enum Family {
+    FAM_GENERIC,         // lqmpc_generic.hip, workspace in HBM
+    FAM_WG,              // lqmpc_wg.hip, one instance per workgroup
+    FAM_SPEC,            // lqmpc_spec.hip, packed register-resident
+    FAM_SPEC_TIERED,     // ... a sorted rollout whose first nwide slots get the 16-lane-row layout, then the packed kernel over its hand-back list
+    FAM_R16,             // lqmpc_r16.hip, prebuilt 16-lane-row kernel on the whole batch, then the packed kernel over its hand-back list
+    FAM_JIT,             // lqmpc_jit.hip, run-time compiled 16-lane-row kernel, then the generic kernel over its hand-back list
+};
+struct Plan {
+    Family family;
+    bool order;          // build the difficulty order (probe + scatter) in front of the first pass
+    bool order_roll;     // the host computes the first gain for the order's key (KParams::order_roll)
+    long long nwide;     // FAM_SPEC_TIERED: slots of the wide tier
+    long long ws_cols;   // workspace columns of the generic kernel; 0: the call needs no workspace
+    // the 16-lane-row kernels on the whole batch: every mode, the sweep fused into one launch (otherwise it is the two-launch fall-back)
+    bool rows() const { return family == FAM_R16 || family == FAM_JIT; }
+    // the hand-back list goes to the generic kernel over a list, with ws_cols columns (otherwise to the packed kernel)
+    bool list_generic() const { return family == FAM_JIT; }
+};
+
+// The routing of one call: a function of the options, the call and the device, nothing else.  The only refusals are a forced kernel
+// that does not serve the shape; a failed run-time compile is not one (lqmpc_last_error says why, the call falls to the next family).
+static int make_plan(const lqmpc_options &o, const Call &c, int device, Plan &pl)
+{
+    const int nx = c.nx, nu = c.nu, N = c.N;
+    const int presolve = o.presolve < 0 ? 1 : o.presolve, warm_start = o.warm_start < 0 ? presolve : o.warm_start;
+    const bool built = lqmpc::spec_available(nx, nu, N);
+    if (o.kernel == LQMPC_KERNEL_SPECIALIZED && !built)
+        return fail(LQMPC_ERR_UNSUPPORTED, "no register-resident specialisation built for these dims");
+    const bool spec = built && o.kernel != LQMPC_KERNEL_GENERIC && o.kernel != LQMPC_KERNEL_WORKGROUP;
+    // a shape without a prebuilt instantiation inside the 16-lane-row domain: compile its kernel now (first use: ~2 s; then cached).
+    // The algorithm is the presolve + warm-started active set, so the option combinations that switch those off stay on the
+    // generic / workgroup kernels, as do the shapes whose compile fails (no hiprtc on the machine: reported by last_error once).
+    bool jit = false;
+    if (o.kernel == LQMPC_KERNEL_AUTO && o.jit != 0 && !built && presolve && warm_start && c.Bsz <= INT32_MAX &&
+        lqmpc::jit_r16_shape(nx, nu, N, nullptr)) {
+        std::string why;
+        jit = lqmpc::jit_available(device, nx, nu, N, c.mode, &why);
+        if (!jit) g_err = "run-time compile unavailable, using the generic kernels: " + why;
+    }
+    const bool wg = !spec && !jit && (o.kernel == LQMPC_KERNEL_AUTO || o.kernel == LQMPC_KERNEL_WORKGROUP) && lqmpc::wg_supported(nx, nu, N);
+    if (o.kernel == LQMPC_KERNEL_WORKGROUP && !wg)
+        return fail(LQMPC_ERR_UNSUPPORTED, "the workgroup kernel needs 32 < N*nu <= 128, nx <= 16, nu <= 8 and an LDS image within 160 KiB");
+    // Which layout where a shape has both specialisations (measured at C3 / C2 shapes).  Rollouts: the
+    // 16-lane-row kernel (two waves per SIMD, P and W packed in LDS) for every batch size -- 0.77 ms against 0.97 ms for the two-tier
+    // launch of the packed kernel at C3's 65 536 instances, and it also fills the GPU where the packed kernel (16 or 32 instances
+    // per wavefront) cannot.  One-shot entry points and the fused sweep (built for one wave per SIMD): up to `limit` instances
+    // (max V_N with n <= 10 and a large batch: the packed kernel's one lane per instance wins the K-state loop, 0.24 against 0.36 ms
+    // at C2 x 65 536).  options.layout = 0/1 forces the choice (0 gives the packed kernel and its two-tier launch).
+    const int64_t limit = (c.mode == lqmpc::MODE_MAXVN && N * nu <= 10) ? 32768 : INT32_MAX;
+    bool r16 = spec && o.kernel == LQMPC_KERNEL_AUTO && presolve && warm_start && lqmpc::r16_available(nx, nu, N) && c.Bsz <= INT32_MAX;
+    if (r16 && lqmpc::r16_lanes(nx, nu, N) == 64) r16 = o.layout != 0;   // vs one wave per instance in the packed family too: always
+    else r16 = r16 && (o.layout >= 0 ? o.layout == 1 : c.Bsz <= limit);
+    pl.family = jit ? FAM_JIT : r16 ? FAM_R16 : spec ? FAM_SPEC : wg ? FAM_WG : FAM_GENERIC;
+
+    // The difficulty order of a rollout (options.order; the two-launch sweep leaves it to the rollout it calls).  The packed family
+    // orders from 1 024 instances; the 16-lane-row family from 8 192 (measured at C3: the sorted walk pays for its probe and scatter
+    // launches from about 8 192 instances: 0.26 against 0.31 ms at 16 384, 0.25 against 0.19 ms at 4 096).
+    const bool rollout = c.mode == lqmpc::MODE_ROLLOUT || c.mode == lqmpc::MODE_SWEEP;
+    const bool packed_size = c.T >= 4 && c.Bsz >= 1024;
+    if (pl.rows()) pl.order = rollout && (o.order < 0 ? (c.T >= 4 && c.Bsz >= 8192) : o.order == 1);
+    else pl.order = c.mode == lqmpc::MODE_ROLLOUT && spec && (o.order < 0 ? (presolve && packed_size) : o.order == 1);
+    // The order's key for rollouts on a shared plant with zero references and a centred box (lqmpc_probe.h): a clipped roll of the
+    // PLANT under the first gain of the N-stage problem on it -- the closed loop every instance of the batch runs in.  Only where an
+    // order can be built at all (the looser of the two sizes): small batches skip the host's Riccati steps.
+    const bool may_order = o.order > 0 || (o.order < 0 && packed_size);
+    pl.order_roll = may_order && rollout && nu <= 8 && !c.true_per_instance && c.At_sh && c.Bt_sh && !has_lin(c);
+    // the hardest instances (first in the order) in the 16-lane-row layout: see lqmpc_spec_tiered_kernel
+    pl.nwide = 0;
+    if (pl.order && pl.family == FAM_SPEC && lqmpc::spec_tiered_available(nx, nu, N) && presolve && warm_start && c.Bsz <= INT32_MAX) {
+        const long long nw = o.nwide >= 0 ? o.nwide : (c.Bsz / 8 < 4096 ? c.Bsz / 8 : 4096) / 4 * 4;   // measured: ~one 16-lane-row wave per SIMD
+        pl.nwide = nw < 0 ? 0 : (nw > c.Bsz ? c.Bsz : nw);
+        if (pl.nwide > 0) pl.family = FAM_SPEC_TIERED;
+    }
+    // Generic workspace: a column per instance of the batch (in whole wavefronts) where the generic kernel runs the call; behind a
+    // run-time compiled kernel it only ever sees the instances that kernel hands back -- a bounded workspace, walked by a
+    // grid-stride loop
+    pl.ws_cols = pl.family == FAM_JIT ? JIT_FALLBACK_COLS : pl.family == FAM_GENERIC ? (c.Bsz + 63) / 64 * 64 : 0;
+    return 0;
+}
+
+static int ensure_ws(lqmpc_handle *h, const Call &c, const Plan &pl)
+{
+    return ensure(h, h->ws, (size_t)lqmpc::generic_ws_entries(c.nx, c.nu, c.N) * (size_t)pl.ws_cols * sizeof(double));
+}
+
+// key, permutation, counters (in front of the hand-back list) and staged records of a difficulty order over B instances
+static int ensure_order(lqmpc_handle *h, int nx, int nu, size_t B)
+{
+    int rc = ensure(h, h->key, B * sizeof(double));
+    if (!rc) rc = ensure(h, h->perm, B * sizeof(int));
+    if (!rc) rc = ensure_fail(h, (B + FAIL_HDR) * sizeof(int));
+    if (!rc) rc = ensure(h, h->rec, B * (size_t)(nx * nx + nx * nu + nx) * sizeof(double));
+    return rc;
+}
+
+// Check the arguments, plan the call under `opt`, pack the batch-shared data, upload it (skipped when identical to the last upload),
+// size the workspace, fill the kernel parameter block.
+static int prepare(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, KParams &p, Plan &pl)
 {
     h->fail_cleared = false;
     int rc = check_dims(c.nx, c.nu, c.N, c.Bsz);
@@ -414,6 +484,8 @@ static int prepare(lqmpc_handle *h, const Call &c, KParams &p)
             return fail(LQMPC_ERR_BAD_ARG, buf);
         }
     HIP_TRY(hipSetDevice(h->device));
+    rc = make_plan(opt, c, h->device, pl);
+    if (rc) return rc;
     const int nx = c.nx, nu = c.nu, N = c.N;
     std::vector<double> sh;
     auto put = [&](const double *src, int count) {
@@ -433,15 +505,8 @@ static int prepare(lqmpc_handle *h, const Call &c, KParams &p)
     p.so.At = put(c.true_per_instance ? nullptr : c.At_sh, nx * nx);
     p.so.Bt = put(c.true_per_instance ? nullptr : c.Bt_sh, nx * nu);
     p.so.x0s = put(c.x0s, c.x0s ? nx * c.K : 1);
-    // the difficulty order's key for rollouts on a shared plant with zero references and a centred box (lqmpc_probe.h): a clipped roll
-    // of the PLANT under the first gain of the N-stage problem on it -- the closed loop every instance of the batch runs in
-    bool lin = c.x_ref || c.u_ref;
-    for (int k = 0; k < nu; ++k) lin = lin || (c.ub[k] + c.lb[k] != 0.0);
-    // (only where an order can be built at all: small batches skip the host's Riccati steps)
-    const bool may_order = h->opt.order > 0 || (h->opt.order < 0 && c.T >= 4 && c.Bsz >= 1024);
-    bool roll = may_order && !lin && !c.true_per_instance && c.At_sh && c.Bt_sh && nu <= 8 && (c.mode == lqmpc::MODE_ROLLOUT || c.mode == lqmpc::MODE_SWEEP);
     std::vector<double> Kg((size_t)nu * nx, 0.0);
-    if (roll) roll = host_first_gain(nx, nu, N, c.At_sh, c.Bt_sh, c.Q, c.R, c.P, Kg.data());
+    const bool roll = pl.order_roll && host_first_gain(nx, nu, N, c.At_sh, c.Bt_sh, c.Q, c.R, c.P, Kg.data());
     p.so.Kg = put(roll ? Kg.data() : nullptr, nu * nx);
     p.order_roll = roll ? 1 : 0;
     rc = ensure(h, h->shared, sh.size() * sizeof(double));
@@ -465,42 +530,18 @@ static int prepare(lqmpc_handle *h, const Call &c, KParams &p)
     p.T = c.T; p.K = c.K; p.mode = c.mode;
     p.true_per_instance = c.true_per_instance;
     p.has_ref = (c.x_ref || c.u_ref) ? 1 : 0;
-    p.has_lin = p.has_ref;
-    for (int k = 0; k < nu; ++k) p.has_lin |= (c.ub[k] + c.lb[k] != 0.0) ? 1 : 0;
-    p.max_iter = h->opt.max_iter; p.polish = h->opt.polish;
-    p.presolve = h->opt.presolve < 0 ? 1 : h->opt.presolve;
-    p.warm_start = h->opt.warm_start < 0 ? p.presolve : h->opt.warm_start;
-    p.eps = h->opt.eps; p.tau = h->opt.tau; p.z0_scale = h->opt.z0_scale;
+    p.has_lin = has_lin(c) ? 1 : 0;
+    p.max_iter = opt.max_iter; p.polish = opt.polish;
+    p.presolve = opt.presolve < 0 ? 1 : opt.presolve;
+    p.warm_start = opt.warm_start < 0 ? p.presolve : opt.warm_start;
+    p.eps = opt.eps; p.tau = opt.tau; p.z0_scale = opt.z0_scale;
     p.Bsz = c.Bsz;
     p.sh = (const double *)h->shared.p;
-    p.r16_maxit = h->opt.r16_maxit;                            // a small cap exercises the hand-back path (tests)
-    p.r16_build = h->opt.r16_build;
-    if (h->opt.kernel == LQMPC_KERNEL_SPECIALIZED && !lqmpc::spec_available(nx, nu, N))
-        return fail(LQMPC_ERR_UNSUPPORTED, "no register-resident specialisation built for these dims");
-    // a shape without a prebuilt instantiation inside the 16-lane-row domain: compile its kernel now (first use: ~2 s; then cached).
-    // The algorithm is the presolve + warm-started active set, so the option combinations that switch those off stay on the
-    // generic / workgroup kernels, as do the shapes whose compile fails (no hiprtc on the machine: reported by last_error once).
-    h->use_jit = false;
-    if (h->opt.kernel == LQMPC_KERNEL_AUTO && h->opt.jit != 0 && !lqmpc::spec_available(nx, nu, N) && p.presolve && p.warm_start &&
-        c.Bsz <= INT32_MAX && lqmpc::jit_r16_shape(nx, nu, N, nullptr)) {
-        std::string why;
-        h->use_jit = lqmpc::jit_available(h->device, nx, nu, N, c.mode, &why);
-        if (!h->use_jit) g_err = "run-time compile unavailable, using the generic kernels: " + why;
-    }
-    h->use_wg = !use_spec(h, nx, nu, N) && !h->use_jit && (h->opt.kernel == LQMPC_KERNEL_AUTO || h->opt.kernel == LQMPC_KERNEL_WORKGROUP) &&
-                lqmpc::wg_supported(p, c.lb, c.ub);
-    if (h->opt.kernel == LQMPC_KERNEL_WORKGROUP && !h->use_wg)
-        return fail(LQMPC_ERR_UNSUPPORTED, "the workgroup kernel needs 32 < N*nu <= 128, nx <= 16, nu <= 8 and an LDS image within 160 KiB");
-    if (h->use_jit) {
-        // the generic kernel only ever sees the instances the 16-lane-row kernel hands back: a bounded workspace, walked by a grid-stride loop
-        p.ws_stride = JIT_FALLBACK_COLS;
-        rc = ensure(h, h->ws, (size_t)lqmpc::generic_ws_entries(nx, nu, N) * (size_t)p.ws_stride * sizeof(double));
-        if (rc) return rc;
-        p.ws = (double *)h->ws.p;
-    } else if (!use_spec(h, nx, nu, N) && !h->use_wg) {
-        p.ws_stride = (c.Bsz + 63) / 64 * 64;
-        const size_t bytes = (size_t)lqmpc::generic_ws_entries(nx, nu, N) * (size_t)p.ws_stride * sizeof(double);
-        rc = ensure(h, h->ws, bytes);
+    p.r16_maxit = opt.r16_maxit;                               // a small cap exercises the hand-back path (tests)
+    p.r16_build = opt.r16_build;
+    if (pl.ws_cols) {
+        p.ws_stride = pl.ws_cols;
+        rc = ensure_ws(h, c, pl);
         if (rc) return rc;
         p.ws = (double *)h->ws.p;
     }
@@ -513,15 +554,10 @@ static int prepare(lqmpc_handle *h, const Call &c, KParams &p)
 // two launches instead of the eight of a full radix / merge sort (41 us of a 0.51 ms C3 launch).  Which instance gets which
 // position inside a bucket depends on the order of the atomics, i.e. the permutation is not reproducible run to run; the
 // results are, because no result depends on the instances that share a wavefront.
-static int build_order(lqmpc_handle *h, KParams &p)
+static int build_order(lqmpc_handle *h, const Plan &pl, KParams &p)
 {
-    const size_t B = (size_t)p.Bsz;
-    if (B > (size_t)INT32_MAX) return fail(LQMPC_ERR_BAD_ARG, "ordering supports up to 2^31-1 instances");
-    int rc = ensure(h, h->key, B * sizeof(double));
-    if (!rc) rc = ensure(h, h->perm, B * sizeof(int));
-    if (!rc) rc = ensure_fail(h, ((size_t)p.Bsz + FAIL_HDR) * sizeof(int));
-    const size_t rec_doubles = (size_t)(p.nx * p.nx + p.nx * p.nu + p.nx);
-    if (!rc) rc = ensure(h, h->rec, B * rec_doubles * sizeof(double));
+    if (p.Bsz > (long long)INT32_MAX) return fail(LQMPC_ERR_BAD_ARG, "ordering supports up to 2^31-1 instances");
+    int rc = ensure_order(h, p.nx, p.nu, (size_t)p.Bsz);
     if (rc) return rc;
     // The hand-back count and the order's counters.  First call (or a new buffer): one fill of everything.  After that the probe
     // launch itself zeroes the count and the set of counters the NEXT call will use (the sets alternate), so a call costs no fill
@@ -541,7 +577,7 @@ static int build_order(lqmpc_handle *h, KParams &p)
     q.fail_count = (int *)h->fail.p;
     q.stage = (double *)h->rec.p;
     const char *name = nullptr;
-    if (h->use_jit) {
+    if (pl.family == FAM_JIT) {
         std::string why;
         if (!lqmpc::launch_jit(h->device, q, h->stream, &name, &why)) return fail(LQMPC_ERR_UNSUPPORTED, "probe launch failed: " + why);
     } else if (!lqmpc::launch_spec(q, h->stream, &name)) return fail(LQMPC_ERR_UNSUPPORTED, "probe launch failed");
@@ -554,12 +590,13 @@ static int build_order(lqmpc_handle *h, KParams &p)
     return 0;
 }
 
-static int launch(lqmpc_handle *h, const KParams &p)
+// one launch of the packed, workgroup or generic kernel on the whole batch
+static int launch(lqmpc_handle *h, const Plan &pl, const KParams &p)
 {
     const char *name = "lqmpc_generic_kernel";
-    if (use_spec(h, p.nx, p.nu, p.N)) {
+    if (pl.family == FAM_SPEC || pl.family == FAM_SPEC_TIERED) {
         if (!lqmpc::launch_spec(p, h->stream, &name)) return fail(LQMPC_ERR_UNSUPPORTED, "specialisation launch failed");
-    } else if (h->use_wg) {
+    } else if (pl.family == FAM_WG) {
         if (!lqmpc::launch_wg(p, h->stream, &name)) return fail(LQMPC_ERR_HIP, "workgroup kernel launch failed");
     } else {
         lqmpc::launch_generic(p, h->stream);
@@ -569,21 +606,6 @@ static int launch(lqmpc_handle *h, const KParams &p)
     return 0;
 }
 
-// Which layout (measured at C3 / C2 shapes).  Rollouts: the 16-lane-row kernel (two waves per SIMD,
-// P and W packed in LDS) for every batch size -- 0.77 ms against 0.97 ms for the two-tier launch of the packed kernel at
-// C3's 65 536 instances, and it also fills the GPU where the packed kernel (16 or 32 instances per wavefront) cannot.
-// One-shot entry points and the fused sweep (built for one wave per SIMD): up to `limit` instances.
-// options.layout = 0/1 forces the choice (0 gives the packed kernel and its two-tier launch).
-static bool use_r16(const lqmpc_handle *h, const KParams &p, int64_t Bsz, int64_t limit)
-{
-    const int force = h->opt.layout;
-    const bool ok = h->opt.kernel == LQMPC_KERNEL_AUTO && p.presolve && p.warm_start && lqmpc::r16_available(p.nx, p.nu, p.N) &&
-                    Bsz <= INT32_MAX;
-    if (ok && lqmpc::r16_lanes(p.nx, p.nu, p.N) == 64) return force != 0;   // vs one wave per instance in the packed family too: always
-    return ok && (force >= 0 ? force == 1 : Bsz <= limit);
-}
-
-// 16-lane-row kernel on the whole batch, then the packed kernel over whatever it handed back (device-side list)
 // the hand-back list of this call: count zeroed (by build_order's fill if it ran), list behind the order's counters
 static int prepare_hand_back(lqmpc_handle *h, KParams &p)
 {
@@ -593,6 +615,20 @@ static int prepare_hand_back(lqmpc_handle *h, KParams &p)
     h->fail_cleared = false;
     p.fail_count = (int *)h->fail.p;
     p.fail_list = (int *)h->fail.p + FAIL_HDR;
+    return 0;
+}
+
+// Second pass: the instances the first pass `p` handed back (status 3, device-side list), from scratch, in `mode` -- on the packed
+// kernel (interior point + polish) where the shape has one, on the generic kernel otherwise.  vn: where V_N goes when p has none.
+static int launch_hand_back(lqmpc_handle *h, const Plan &pl, const KParams &p, int mode, double *vn)
+{
+    KParams f = p;
+    f.mode = mode;
+    f.perm = p.fail_list; f.count_dev = p.fail_count; f.fail_list = nullptr; f.fail_count = nullptr; f.nwide = 0;
+    if (!f.VN) f.VN = vn;
+    if (pl.list_generic()) lqmpc::launch_generic_list(f, (int)pl.ws_cols, h->stream);
+    else if (!lqmpc::launch_spec(f, h->stream, nullptr)) return fail(LQMPC_ERR_UNSUPPORTED, "hand-back launch failed");
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -607,39 +643,32 @@ __global__ void lqmpc_merge_listed_kernel(int *st, int *it, const int *st2, cons
     }
 }
 
-static int launch_r16_with_hand_back(lqmpc_handle *h, KParams &p)
+// 16-lane-row kernel (prebuilt or run-time compiled) on the whole batch, then the hand-back pass over whatever it listed
+static int launch_rows(lqmpc_handle *h, const Plan &pl, KParams &p)
 {
     int rc = prepare_hand_back(h, p);
     if (rc) return rc;
     const char *name = nullptr;
-    if (h->use_jit) {
+    if (pl.family == FAM_JIT) {
         std::string why;
         if (!lqmpc::launch_jit(h->device, p, h->stream, &name, &why)) return fail(LQMPC_ERR_HIP, "run-time compiled kernel: " + why);
     } else if (!lqmpc::launch_r16(p, h->stream, &name)) return fail(LQMPC_ERR_UNSUPPORTED, "r16 launch failed");
     HIP_TRY(hipGetLastError());
-    KParams f = p;
-    f.perm = p.fail_list; f.count_dev = p.fail_count; f.fail_list = nullptr; f.fail_count = nullptr; f.nwide = 0;
-    const char *name2 = nullptr;
-    // second pass over the hand-back list: the packed kernel (interior point + polish) where the shape has one, the generic kernel otherwise
-    auto second = [&](const KParams &g) -> bool {
-        if (h->use_jit) { lqmpc::launch_generic_list(g, JIT_FALLBACK_COLS, h->stream); return true; }
-        return lqmpc::launch_spec(g, h->stream, &name2);
-    };
-    if (p.mode == lqmpc::MODE_SWEEP) {         // the packed kernel has no fused mode: max V_N, then the rollout, over the list
+    const bool sweep = p.mode == lqmpc::MODE_SWEEP;
+    if (sweep) {                               // neither second-pass kernel has a fused mode: max V_N, then the rollout, over the list
         // the two passes write status / iters of the listed instances: the max-V_N pass into side buffers, merged below
         // (status = the worse of the two parts, iters = their sum -- the contract of lqmpc_sweep_batch, as on the two-launch path)
         if (p.status) { rc = ensure(h, h->st2, (size_t)p.Bsz * sizeof(int32_t)); if (rc) return rc; }
         if (p.iters) { rc = ensure(h, h->it2, (size_t)p.Bsz * sizeof(int32_t)); if (rc) return rc; }
-        f.mode = lqmpc::MODE_MAXVN;
-        f.status = p.status ? (int *)h->st2.p : nullptr;
-        f.iters = p.iters ? (int *)h->it2.p : nullptr;
-        if (!second(f)) return fail(LQMPC_ERR_UNSUPPORTED, "hand-back launch failed");
-        f.mode = lqmpc::MODE_ROLLOUT;
-        f.status = p.status; f.iters = p.iters;
+        KParams m = p;
+        m.status = p.status ? (int *)h->st2.p : nullptr;
+        m.iters = p.iters ? (int *)h->it2.p : nullptr;
+        rc = launch_hand_back(h, pl, m, lqmpc::MODE_MAXVN, nullptr);
+        if (rc) return rc;
     }
-    if (!second(f)) return fail(LQMPC_ERR_UNSUPPORTED, "hand-back launch failed");
-    HIP_TRY(hipGetLastError());
-    if (p.mode == lqmpc::MODE_SWEEP && (p.status || p.iters)) {
+    rc = launch_hand_back(h, pl, p, sweep ? (int)lqmpc::MODE_ROLLOUT : p.mode, nullptr);
+    if (rc) return rc;
+    if (sweep && (p.status || p.iters)) {
         const unsigned blocks = (unsigned)(p.Bsz < 65536 ? (p.Bsz + 255) / 256 : 256);
         hipLaunchKernelGGL(lqmpc_merge_listed_kernel, dim3(blocks), dim3(256), 0, h->stream, p.status, p.iters,
                            (const int *)h->st2.p, (const int *)h->it2.p, (const int *)p.fail_list, (const int *)p.fail_count);
@@ -657,6 +686,18 @@ __global__ void lqmpc_merge_status_kernel(int *st, int *it, const int *st2, cons
     if (it) it[i] += it2[i];
 }
 
+// lqmpc_solve_batch_dev under explicit options (a prepared controller passes through here under its own snapshot)
+static int solve_dev(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, const double *dA, const double *dB, const double *dx0,
+                     double *du0, double *dVN, int32_t *dstatus, int32_t *diters)
+{
+    KParams p;
+    Plan pl;
+    int rc = prepare(h, opt, c, p, pl);
+    if (rc) return rc;
+    p.A = dA; p.B = dB; p.x0 = dx0; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
+    return pl.rows() ? launch_rows(h, pl, p) : launch(h, pl, p);
+}
+
 extern "C" {
 
 int lqmpc_reserve(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T)
@@ -668,22 +709,14 @@ int lqmpc_reserve(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T)
     HIP_TRY(hipSetDevice(h->device));
     rc = ensure(h, h->shared, 8192 * sizeof(double));
     if (rc) return rc;
-    const bool fast = use_spec(h, nx, nu, N) || (h->opt.kernel == LQMPC_KERNEL_AUTO && h->opt.jit != 0 && lqmpc::jit_r16_shape(nx, nu, N, nullptr));
-    if (fast) {
-        // the hand-back list / order counters of the 16-lane-row kernels, and -- for rollouts long and large enough to be walked in
-        // difficulty order (T >= 4: lqmpc_rollout_batch_dev) -- the key, permutation and record buffers of the order
-        rc = ensure_fail(h, ((size_t)Bsz + FAIL_HDR) * sizeof(int));
-        if (!rc && T >= 4 && Bsz >= 1024) {
-            rc = ensure(h, h->key, (size_t)Bsz * sizeof(double));
-            if (!rc) rc = ensure(h, h->perm, (size_t)Bsz * sizeof(int));
-            if (!rc) rc = ensure(h, h->rec, (size_t)Bsz * (size_t)(nx * nx + nx * nu + nx) * sizeof(double));
-        }
-    }
-    if (!rc && !use_spec(h, nx, nu, N)) {
-        const bool wg_only = !fast && N * nu > 32;          // (the workgroup kernel needs no workspace)
-        const size_t cols = fast ? (size_t)JIT_FALLBACK_COLS : (size_t)(Bsz + 63) / 64 * 64;
-        if (!wg_only) rc = ensure(h, h->ws, (size_t)lqmpc::generic_ws_entries(nx, nu, N) * cols * sizeof(double));
-    }
+    // no box, references or mode here: the plan of the widest call of this shape under the handle's options -- a rollout of T steps
+    // on a per-instance plant, a one-shot solve without T -- and the buffers that call sizes
+    const Call c{nx, nu, N, T, 0, T > 0 ? lqmpc::MODE_ROLLOUT : lqmpc::MODE_SOLVE, 1, Bsz};
+    Plan pl;
+    rc = make_plan(h->opt, c, h->device, pl);
+    if (!rc && (pl.rows() || pl.family == FAM_SPEC_TIERED)) rc = ensure_fail(h, ((size_t)Bsz + FAIL_HDR) * sizeof(int));
+    if (!rc && pl.order) rc = ensure_order(h, nx, nu, (size_t)Bsz);
+    if (!rc && pl.ws_cols) rc = ensure_ws(h, c, pl);
     return rc;
 }
 
@@ -693,13 +726,8 @@ int lqmpc_solve_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, c
                           int32_t *dstatus, int32_t *diters)
 {
     if (!h || !dA || !dB || !dx0 || !du0 || !dVN) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
-    Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
-    KParams p;
-    int rc = prepare(h, c, p);
-    if (rc) return rc;
-    p.A = dA; p.B = dB; p.x0 = dx0; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
-    if (h->use_jit || (use_spec(h, nx, nu, N) && use_r16(h, p, Bsz, INT32_MAX))) return launch_r16_with_hand_back(h, p);
-    return launch(h, p);
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
+    return solve_dev(h, h->opt, c, dA, dB, dx0, du0, dVN, dstatus, diters);
 }
 
 int lqmpc_rollout_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *dA, const double *dB,
@@ -713,45 +741,22 @@ int lqmpc_rollout_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
     Call c{nx, nu, N, T, 0, lqmpc::MODE_ROLLOUT, true_per_instance ? 1 : 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref,
            A_true, B_true, nullptr};
     KParams p;
-    int rc = prepare(h, c, p);
+    Plan pl;
+    int rc = prepare(h, h->opt, c, p, pl);
     if (rc) return rc;
     p.A = dA; p.B = dB; p.x0 = dx0; p.JT = dJT; p.X = dX; p.U = dU; p.status = dstatus; p.iters = diters;
     if (true_per_instance) { p.At = A_true; p.Bt = B_true; }
-    const bool spec = use_spec(h, nx, nu, N);
-    const int order = h->opt.order < 0 ? ((spec && p.presolve && T >= 4 && Bsz >= 1024) ? 1 : 0) : (spec ? h->opt.order : 0);
-    if (h->use_jit || (spec && use_r16(h, p, Bsz, INT32_MAX))) {
-        // (measured at C3: the sorted walk pays for its probe and scatter launches from about 8 192 instances: 0.26 against 0.31 ms
-        // at 16 384, 0.25 against 0.19 ms at 4 096)
-        const int r16_order = h->opt.order < 0 ? ((T >= 4 && Bsz >= 8192) ? 1 : 0) : h->opt.order;
-        if (r16_order) {
-            rc = build_order(h, p);
-            if (rc) return rc;
-        }
-        return launch_r16_with_hand_back(h, p);
-    }
-    if (order) {
-        rc = build_order(h, p);
+    if (pl.order) {
+        rc = build_order(h, pl, p);
         if (rc) return rc;
-        // the hardest instances (first in the order) in the 16-lane-row layout: see lqmpc_spec_tiered_kernel
-        if (lqmpc::spec_tiered_available(nx, nu, N) && p.presolve && p.warm_start && Bsz <= INT32_MAX) {
-            long long nw = h->opt.nwide >= 0 ? h->opt.nwide : (Bsz / 8 < 4096 ? Bsz / 8 : 4096) / 4 * 4;   // measured: ~one 16-lane-row wave per SIMD
-            p.nwide = nw < 0 ? 0 : (nw > Bsz ? Bsz : nw);
-        }
-        if (p.nwide > 0) {
-            rc = prepare_hand_back(h, p);
-            if (rc) return rc;
-            rc = launch(h, p);
-            if (rc) return rc;
-            const char *name = h->last_kernel;
-            // second pass: whatever the wide tier handed back (status 3), packed, from the start of the rollout
-            KParams f = p;
-            f.perm = p.fail_list; f.count_dev = p.fail_count; f.fail_list = nullptr; f.fail_count = nullptr; f.nwide = 0;
-            rc = launch(h, f);
-            h->last_kernel = name;
-            return rc;
-        }
     }
-    return launch(h, p);
+    if (pl.rows()) return launch_rows(h, pl, p);
+    if (pl.family != FAM_SPEC_TIERED) return launch(h, pl, p);
+    p.nwide = pl.nwide;
+    rc = prepare_hand_back(h, p);
+    if (!rc) rc = launch(h, pl, p);
+    // second pass: whatever the wide tier handed back (status 3), packed, from the start of the rollout
+    return rc ? rc : launch_hand_back(h, pl, p, p.mode, nullptr);
 }
 
 int lqmpc_max_vn_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int K, const double *dA, const double *dB,
@@ -763,12 +768,11 @@ int lqmpc_max_vn_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, 
     if (K < 1 || K > 1024) return fail(LQMPC_ERR_BAD_ARG, "K must be in [1,1024]");
     Call c{nx, nu, N, 0, K, lqmpc::MODE_MAXVN, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, x0s};
     KParams p;
-    int rc = prepare(h, c, p);
+    Plan pl;
+    int rc = prepare(h, h->opt, c, p, pl);
     if (rc) return rc;
     p.A = dA; p.B = dB; p.MV = dMV; p.status = dstatus; p.iters = diters;
-    // (n <= 10 and a large batch: the packed kernel's one lane per instance wins the K-state loop, 0.24 against 0.36 ms at C2 x 65 536)
-    if (h->use_jit || (use_spec(h, nx, nu, N) && use_r16(h, p, Bsz, N * nu <= 10 ? 32768 : INT32_MAX))) return launch_r16_with_hand_back(h, p);
-    return launch(h, p);
+    return pl.rows() ? launch_rows(h, pl, p) : launch(h, pl, p);
 }
 
 int lqmpc_sweep_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, int K, const double *dA, const double *dB,
@@ -782,20 +786,20 @@ int lqmpc_sweep_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, i
     if (K < 1 || K > 1024) return fail(LQMPC_ERR_BAD_ARG, "K must be in [1,1024]");
     Call c{nx, nu, N, T, K, lqmpc::MODE_SWEEP, true_per_instance ? 1 : 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, A_true, B_true, x0s};
     KParams p;
-    int rc = prepare(h, c, p);
+    Plan pl;
+    int rc = prepare(h, h->opt, c, p, pl);
     if (rc) return rc;
-    if (h->use_jit || (use_spec(h, nx, nu, N) && use_r16(h, p, Bsz, INT32_MAX))) {
+    if (pl.rows()) {
         // one launch: condensing and W once per instance, K open-loop QPs, then the closed loop
         p.A = dA; p.B = dB; p.x0 = dx0; p.JT = dJT; p.MV = dMV; p.status = dstatus; p.iters = diters;
         if (true_per_instance) { p.At = A_true; p.Bt = B_true; }
-        const int order = h->opt.order < 0 ? ((T >= 4 && Bsz >= 8192) ? 1 : 0) : h->opt.order;
-        if (order) {
-            rc = build_order(h, p);
+        if (pl.order) {
+            rc = build_order(h, pl, p);
             if (rc) return rc;
         }
-        return launch_r16_with_hand_back(h, p);
+        return launch_rows(h, pl, p);
     }
-    // no fused kernel for this shape / size: the two launches, status = worse of the two, iters = their sum
+    // no fused kernel for this shape / size: the two launches (each plans for itself), status = worse of the two, iters = their sum
     int32_t *st2 = nullptr, *it2 = nullptr;
     if (dstatus) { rc = ensure(h, h->st2, (size_t)Bsz * sizeof(int32_t)); if (rc) return rc; st2 = (int32_t *)h->st2.p; }
     if (diters) { rc = ensure(h, h->it2, (size_t)Bsz * sizeof(int32_t)); if (rc) return rc; it2 = (int32_t *)h->it2.p; }
@@ -1142,7 +1146,7 @@ int lqmpc_timer_end(lqmpc_handle *h, float *ms)
 // Prepared controllers: the per-instance set-up kept in HBM, one QP per instance and call from it (kernels: lqmpc_ctl.hip).
 struct lqmpc_controller {
     lqmpc_handle *h = nullptr;
-    lqmpc_options opt;                        // the handle's options when the controller was made: every step runs under these
+    lqmpc_options opt;                        // the handle's options when the controller was made: every step is planned and filled from these
     int nx = 0, nu = 0, N = 0;
     int64_t Bsz = 0;
     std::vector<double> Q, R, P, lb, ub, xref, uref;
@@ -1177,14 +1181,6 @@ Call ctl_call(const lqmpc_controller *c)
                 c->has_xref ? c->xref.data() : nullptr, c->has_uref ? c->uref.data() : nullptr, nullptr, nullptr, nullptr};
 }
 
-// the handle under the controller's options for the length of one call
-struct OptScope {
-    lqmpc_handle *h;
-    lqmpc_options saved;
-    OptScope(lqmpc_handle *h_, const lqmpc_options &o) : h(h_), saved(h_->opt) { h->opt = o; }
-    ~OptScope() { h->opt = saved; }
-};
-
 int ctl_launch(lqmpc_controller *c, const KParams &p)
 {
     lqmpc_handle *h = c->h;
@@ -1210,10 +1206,11 @@ int ctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double
 {
     if (out) *out = nullptr;
     if (!h || !out || !A || !B) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
-    // the argument checks, the shared block and the routing decisions of an ordinary solve on this handle
+    // the argument checks, the shared block and the plan of an ordinary solve on this handle
     Call c0{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
     KParams p;
-    int rc = prepare(h, c0, p);
+    Plan pl;
+    int rc = prepare(h, h->opt, c0, p, pl);
     if (rc) return rc;
     lqmpc_controller *c = new lqmpc_controller();
     c->h = h; c->opt = h->opt; c->nx = nx; c->nu = nu; c->N = N; c->Bsz = Bsz;
@@ -1221,10 +1218,9 @@ int ctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double
     c->lb.assign(lb, lb + nu); c->ub.assign(ub, ub + nu);
     if (x_ref) { c->xref.assign(x_ref, x_ref + nx * N); c->has_xref = true; }
     if (u_ref) { c->uref.assign(u_ref, u_ref + nu * N); c->has_uref = true; }
-    // fast path: exactly where lqmpc_solve_batch_dev runs the 16-lane-row family under these options
-    const bool r16 = use_spec(h, nx, nu, N) && use_r16(h, p, Bsz, INT32_MAX);
-    if (r16 || h->use_jit) {
-        if (r16 && lqmpc::ctl_available(nx, nu, N)) c->fast = true;
+    // fast path: where that plan runs the 16-lane-row family
+    if (pl.rows()) {
+        if (pl.family == FAM_R16 && lqmpc::ctl_available(nx, nu, N)) c->fast = true;
         else if (h->opt.jit != 0) {
             std::string why;
             c->fast = c->jit = lqmpc::jit_available(h->device, nx, nu, N, lqmpc::MODE_CTL_FACTOR, &why) &&
@@ -1284,18 +1280,17 @@ int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0
     if (!c || !dx || !du0) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
     lqmpc_handle *h = c->h;
     HIP_TRY(hipSetDevice(h->device));
-    OptScope scope(h, c->opt);
     const Call cl = ctl_call(c);
     if (!c->fast) {
         // pass-through: the existing solve path, unchanged, on the controller's copies of A and B
         if (!dVN && !c->vn) { int rc = ctl_alloc(c, &c->vn, (size_t)c->Bsz * sizeof(double)); if (rc) return rc; }
-        int rc = lqmpc_solve_batch_dev(h, c->nx, c->nu, c->N, c->Bsz, (const double *)c->A, (const double *)c->B, cl.Q, cl.R, cl.P, cl.lb, cl.ub,
-                                       dx, cl.x_ref, cl.u_ref, du0, dVN ? dVN : (double *)c->vn, dstatus, diters);
+        int rc = solve_dev(h, c->opt, cl, (const double *)c->A, (const double *)c->B, dx, du0, dVN ? dVN : (double *)c->vn, dstatus, diters);
         if (!rc) c->name = h->last_kernel;
         return rc;
     }
     KParams p;
-    int rc = prepare(h, cl, p);
+    Plan pl;
+    int rc = prepare(h, c->opt, cl, p, pl);
     if (rc) return rc;
     ctl_bind(c, p);
     p.x0 = dx; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
@@ -1305,17 +1300,10 @@ int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0
     rc = ctl_launch(c, p);
     if (rc) return rc;
     // whatever did not settle within r16_maxit iterations (or arrived with a non-finite state): the existing kernels, from scratch, over
-    // the device-side list -- as launch_r16_with_hand_back does for a one-shot solve
-    KParams f = p;
-    f.mode = lqmpc::MODE_SOLVE;
-    f.perm = p.fail_list; f.count_dev = p.fail_count; f.fail_list = nullptr; f.fail_count = nullptr; f.nwide = 0;
-    if (!f.VN) {
-        if (!c->vn) { rc = ctl_alloc(c, &c->vn, (size_t)c->Bsz * sizeof(double)); if (rc) return rc; }
-        f.VN = (double *)c->vn;
-    }
-    if (h->use_jit) lqmpc::launch_generic_list(f, JIT_FALLBACK_COLS, h->stream);
-    else if (!lqmpc::launch_spec(f, h->stream, nullptr)) return fail(LQMPC_ERR_UNSUPPORTED, "hand-back launch failed");
-    HIP_TRY(hipGetLastError());
+    // the device-side list -- as launch_rows does for a one-shot solve
+    if (!dVN && !c->vn) { rc = ctl_alloc(c, &c->vn, (size_t)c->Bsz * sizeof(double)); if (rc) return rc; }
+    rc = launch_hand_back(h, pl, p, lqmpc::MODE_SOLVE, (double *)c->vn);
+    if (rc) return rc;
     h->last_kernel = c->name.c_str();
     return 0;
 }

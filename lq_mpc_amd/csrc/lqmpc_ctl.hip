@@ -11,30 +11,18 @@
 // and the state the model expected next) and warm-starts the next one: shifted by one stage as the rollout shifts it when the state
 // advanced, unshifted when it stayed.
 #include "lqmpc_r16_body.h"
+#include "lqmpc_launch.h"
 
 namespace lqmpc {
 
-// register / LDS budget: as the one-shot kernels of the same shape (R16Build in lqmpc_r16.hip)
-template <int NX, int NU, int N, int LPI>
-struct CtlBuild {
-    static constexpr int OCC = ((LPI == 16 && N * NU > 10) || LPI == 64) ? 2 : 1;
-    static constexpr long long LDS_BYTES = (long long)(64 / LPI) * R16<NX, NU, N, LPI, (OCC == 2)>::INST * 8;
-    static constexpr int WAVES = ((OCC == 2 || (N * NU <= 10 && LPI == 16)) && LDS_BYTES * 8 <= 160 * 1024) ? 2 : 1;
-};
-
+// register / LDS budget: as the one-shot kernels of the same shape (R16Build)
 template <int NX, int NU, int N, int MODE, int LPI>
-__global__ void __launch_bounds__(64, (CtlBuild<NX, NU, N, LPI>::WAVES)) lqmpc_ctl_kernel(KParams p)
+__global__ void __launch_bounds__(64, (R16Build<NX, NU, N, LPI>::WAVES)) lqmpc_ctl_kernel(KParams p)
 {
-    using C = R16<NX, NU, N, LPI, (CtlBuild<NX, NU, N, LPI>::OCC == 2)>;
+    using C = R16<NX, NU, N, LPI, (R16Build<NX, NU, N, LPI>::OCC == 2)>;
     __shared__ double lds_raw[C::IPW * C::INST];
-    r16_body<NX, NU, N, MODE, LPI, CtlBuild<NX, NU, N, LPI>::OCC>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
+    r16_body<NX, NU, N, MODE, LPI, R16Build<NX, NU, N, LPI>::OCC>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
 }
-
-struct CtlEntry {
-    int nx, nu, N, lpi;
-    const char *name;
-    void (*launch)(const KParams &, hipStream_t);
-};
 
 template <int NX, int NU, int N, int LPI>
 static void launch_ctl_one(const KParams &p, hipStream_t stream)
@@ -46,15 +34,15 @@ static void launch_ctl_one(const KParams &p, hipStream_t stream)
 }
 
 // the prebuilt shapes; every other shape of the 16-lane-row domain is compiled at run time (lqmpc_jit.hip)
-static const CtlEntry g_ctl[] = {
+static const ShapeEntry g_ctl[] = {
     {4, 2, 10, 16, "lqmpc_ctl_r16_kernel<4,2,10>", launch_ctl_one<4, 2, 10, 16>},
     {2, 1, 10, 16, "lqmpc_ctl_r16_kernel<2,1,10>", launch_ctl_one<2, 1, 10, 16>},
     {4, 2, 20, 64, "lqmpc_ctl_r64_kernel<4,2,20>", launch_ctl_one<4, 2, 20, 64>},
 };
 
-static const CtlEntry *find_ctl(int nx, int nu, int N)
+static const ShapeEntry *find_ctl(int nx, int nu, int N)
 {
-    for (const CtlEntry &e : g_ctl)
+    for (const ShapeEntry &e : g_ctl)
         if (e.nx == nx && e.nu == nu && e.N == N) return &e;
     return nullptr;
 }
@@ -64,7 +52,7 @@ bool ctl_available(int nx, int nu, int N) { return find_ctl(nx, nu, N) != nullpt
 // p.mode: MODE_CTL_FACTOR or MODE_CTL_STEP
 bool launch_ctl(const KParams &p, hipStream_t stream, const char **name)
 {
-    const CtlEntry *e = find_ctl(p.nx, p.nu, p.N);
+    const ShapeEntry *e = find_ctl(p.nx, p.nu, p.N);
     if (!e || (p.mode != MODE_CTL_FACTOR && p.mode != MODE_CTL_STEP)) return false;
     e->launch(p, stream);
     if (name) *name = e->name;

@@ -11,6 +11,7 @@
 //                   min 1/2 v'Pv + q'v, |v| <= h, with a dense Cholesky of P + diag(z/s) per
 //                   iteration; optional polish = exact solve on the identified active set.
 #include "lqmpc_common.h"
+#include "lqmpc_launch.h"
 
 namespace lqmpc {
 

@@ -7,9 +7,8 @@
 // objects are kept in memory for the process and, when a cache directory is set (lqmpc_jit_cache_dir; the Python binding points it
 // at the package), on disk across processes.  hiprtc is loaded with dlopen: a machine without it falls back to the generic kernel.
 // The compile itself needs no GPU (lqmpc_jit_compile can pre-build code objects on a build machine).
-#include "lqmpc_common.h"
-#include "lqmpc_r16_body.h"        // (host side: the LDS-size arithmetic of R16 is checked against the templates below)
-#include "lqmpc_bounds_chip.h"
+#include "lqmpc_launch.h"
+#include "lqmpc_bounds_chip.h"     // (host side: the LDS-size arithmetic of BigT is checked against the template below)
 #include "../../include/lqmpc.h"
 
 #include <hip/hiprtc.h>
@@ -41,32 +40,7 @@ bool jit_r16_shape(int nx, int nu, int N, int *lpi)
     if (lpi) *lpi = n <= 32 ? 16 : 64;
     return true;
 }
-
-// R16<NX, NU, N, LPI, PACKED>::INST restated for run-time dimensions (doubles of LDS per instance)
-static int r16_inst(int nx, int nu, int N, int lpi, bool packed)
-{
-    const int n = N * nu, rb = (n + lpi - 1) / lpi, cs = 4 * (((n + 1) / 2 + 3) / 4), ldw = n + 1;
-    const int pk = packed ? n * (n + 1) / 2 : n * ldw, vec = lpi * rb;
-    const int cn0 = 3 * nx * nx + nu * nu + nx * nu, cn1 = (nx > nu ? nx : nu) * (2 * nx + 2 * nu), cn = cn0 > cn1 ? cn0 : cn1;
-    const int oR = 2 * pk, oL = oR + 3 * vec, oC = oL + cs / 2;
-    const int setup = n * nx, end = oC + cn + (cn & 1), oD = end > setup ? end : setup;
-    return oD + 2;
-}
-static_assert(R16<4, 2, 10, 16, true>::INST == 584 && R16<2, 1, 30, 16, true>::INST == 1052 && R16<4, 2, 20, 64, true>::INST == 1904,
-              "r16_inst() below restates this arithmetic: keep the two in step");
-
-struct Build { int lpi, occ, waves, inst; };
-static Build r16_build(int nx, int nu, int N)
-{
-    Build b{};
-    jit_r16_shape(nx, nu, N, &b.lpi);
-    const int n = N * nu;
-    b.occ = ((b.lpi == 16 && n > 10) || b.lpi == 64) ? 2 : 1;             // as R16Build in lqmpc_r16.hip
-    b.inst = r16_inst(nx, nu, N, b.lpi, b.occ == 2);
-    const long long lds = (long long)(64 / b.lpi) * b.inst * 8;
-    b.waves = (lds * 8 <= 160 * 1024) ? 2 : 1;                            // two waves per SIMD only where their LDS fits
-    return b;
-}
+static int jit_lanes(int nx, int nu, int N) { int l = 0; jit_r16_shape(nx, nu, N, &l); return l; }
 
 // ---- hiprtc through dlopen ----
 struct Rtc {
@@ -150,12 +124,15 @@ static std::string program_text(int nx, int nu, int N, int mode)
                  "{ probe_body<%d, %d, %d>(p); }\n}\n", nx, nu, N);
         return buf;
     }
-    const Build b = r16_build(nx, nu, N);
+    // registers, waves per SIMD and the packed flag: R16Build, as the prebuilt kernels of lqmpc_r16.hip / lqmpc_ctl.hip
+    int lpi = 0;
+    jit_r16_shape(nx, nu, N, &lpi);
     snprintf(buf, sizeof buf,
-             "#include \"lqmpc_r16_body.h\"\nnamespace lqmpc {\nextern \"C\" __global__ void __launch_bounds__(64, %d) lqmpc_jit_kernel(KParams p)\n"
-             "{\n    using C = R16<%d, %d, %d, %d, %s>;\n    __shared__ double lds_raw[C::IPW * C::INST];\n"
-             "    r16_body<%d, %d, %d, %d, %d, %d>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);\n}\n}\n",
-             b.waves, nx, nu, N, b.lpi, b.occ == 2 ? "true" : "false", nx, nu, N, mode, b.lpi, b.occ);
+             "#include \"lqmpc_r16_body.h\"\nnamespace lqmpc {\nusing B = R16Build<%d, %d, %d, %d>;\n"
+             "extern \"C\" __global__ void __launch_bounds__(64, (B::WAVES)) lqmpc_jit_kernel(KParams p)\n"
+             "{\n    using C = R16<%d, %d, %d, %d, (B::OCC == 2)>;\n    __shared__ double lds_raw[C::IPW * C::INST];\n"
+             "    r16_body<%d, %d, %d, %d, %d, B::OCC>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);\n}\n}\n",
+             nx, nu, N, lpi, nx, nu, N, lpi, nx, nu, N, mode, lpi);
     return buf;
 }
 
@@ -258,8 +235,7 @@ static const Loaded *get_kernel(int device, int nx, int nu, int N, int mode, std
     }
     if (mode < JIT_BOUNDS_SMALL && !g_names.count(Key{nx, nu, N, 0})) {
         char nm[96];
-        const Build b = r16_build(nx, nu, N);
-        snprintf(nm, sizeof nm, "lqmpc_r%d_jit_kernel<%d,%d,%d>", b.lpi, nx, nu, N);
+        snprintf(nm, sizeof nm, "lqmpc_r%d_jit_kernel<%d,%d,%d>", jit_lanes(nx, nu, N), nx, nu, N);
         g_names[Key{nx, nu, N, 0}] = nm;
     }
     return &(g_loaded[lk] = l);
@@ -283,7 +259,7 @@ bool launch_jit(int device, const KParams &p, hipStream_t stream, const char **n
     unsigned grid;
     if (p.mode == MODE_PROBE) grid = (unsigned)((p.Bsz + 63) / 64);
     else {
-        const int ipw = 64 / r16_build(p.nx, p.nu, p.N).lpi;
+        const int ipw = 64 / jit_lanes(p.nx, p.nu, p.N);
         grid = (unsigned)((p.Bsz + ipw - 1) / ipw);
     }
     KParams arg = p;
@@ -296,8 +272,6 @@ bool launch_jit(int device, const KParams &p, hipStream_t stream, const char **n
     }
     return true;
 }
-
-int jit_lanes(int nx, int nu, int N) { int l = 0; return jit_r16_shape(nx, nu, N, &l) ? l : 0; }
 
 // the on-chip pair of bound-coefficient kernels (lqmpc_bounds_chip.h) of a shape without prebuilt ones: nx <= 8, nu <= 4, any N nu <= 128
 bool jit_bounds_shape(int nx, int nu, int N)

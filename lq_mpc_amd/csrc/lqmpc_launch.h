@@ -1,0 +1,50 @@
+// lqmpc_launch.h -- what the kernel files offer the host side (lqmpc_api.hip), declared once: the defining files include it as well,
+// so a signature that drifts is a compile error.  Host only (not part of the run-time compiled text).
+#pragma once
+#include "lqmpc_common.h"
+#include "lqmpc_bounds.h"
+
+#include <string>
+
+namespace lqmpc {
+
+// one row of a table of prebuilt 16-lane-row instantiations (lqmpc_r16.hip, lqmpc_ctl.hip)
+struct ShapeEntry {
+    int nx, nu, N, lpi;
+    const char *name;
+    void (*launch)(const KParams &, hipStream_t);
+};
+
+// lqmpc_generic.hip: any shape within the build limits, workspace in HBM (ws_stride instances per entry row)
+long long generic_ws_entries(int nx, int nu, int N);
+void launch_generic(const KParams &p, hipStream_t stream);
+// ... over a device-side list (p.perm, p.count_dev) with `cols` workspace columns
+void launch_generic_list(const KParams &p, int cols, hipStream_t stream);
+
+// lqmpc_spec.hip: the packed register-resident kernels; spec_available is false when no specialisation is built for (nx,nu,N)
+bool spec_available(int nx, int nu, int N);
+bool spec_tiered_available(int nx, int nu, int N);
+bool launch_spec(const KParams &p, hipStream_t stream, const char **name);
+void launch_order_scatter(const KParams &p, int *perm, hipStream_t stream);
+
+// lqmpc_r16.hip: one instance per 16-lane row (n <= 32) or per wavefront; lqmpc_r16_lat.hip: the latency build of some of its shapes
+bool r16_available(int nx, int nu, int N);
+int r16_lanes(int nx, int nu, int N);       // 16, 64 (one instance per wavefront: n > 32) or 0
+bool launch_r16(const KParams &p, hipStream_t stream, const char **name);
+bool launch_r16_lat(const KParams &p, hipStream_t stream);
+
+// lqmpc_wg.hip: one instance per workgroup, 32 < n <= 128
+bool wg_supported(int nx, int nu, int N);
+bool launch_wg(const KParams &p, hipStream_t stream, const char **name);
+
+// lqmpc_jit.hip: the 16-lane-row kernel (and the probe) of a shape without a prebuilt instantiation, compiled at run time
+bool jit_r16_shape(int nx, int nu, int N, int *lpi);
+bool jit_available(int device, int nx, int nu, int N, int mode, std::string *why);
+bool launch_jit(int device, const KParams &p, hipStream_t stream, const char **name, std::string *why);
+bool launch_jit_bounds(int device, const BoundsParams &p, hipStream_t stream, std::string *why);
+
+// lqmpc_ctl.hip: the factor / step kernels of a prepared controller (p.mode = MODE_CTL_FACTOR / MODE_CTL_STEP), prebuilt shapes
+bool ctl_available(int nx, int nu, int N);
+bool launch_ctl(const KParams &p, hipStream_t stream, const char **name);
+
+}  // namespace lqmpc

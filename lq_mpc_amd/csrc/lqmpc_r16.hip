@@ -16,40 +16,24 @@
 // row_newbcast: the pivot row reaches the 16 lanes of an instance without leaving the vector registers).  W itself
 // comes from P by the same elimination.
 //
-// Used for whole batches of every size (all entry points; the host picks, lqmpc_api.hip: use_r16) and as the wide
+// Used for whole batches of every size (all entry points; the host picks, lqmpc_api.hip: make_plan) and as the wide
 // tier of the packed family's sorted rollouts (lqmpc_spec_tiered_kernel, options.layout = 0).
 // An instance whose active set does not settle within the iteration cap is reported with status 3 internally; the
 // host re-runs exactly those instances on the packed kernel (interior point + active-set finishing) in a second
 // launch over a device-side list.
 #include <cstdio>
 #include "lqmpc_r16_body.h"
+#include "lqmpc_launch.h"
 
 namespace lqmpc {
 
-// Register budget: two waves per SIMD (256 registers) -- the n <= 10 shapes as they are, the larger 16-lane shapes and the
-// one-instance-per-wavefront mapping in the low-register build (OCC = 2: rolled set-up loops, packed W, constants in LDS).
-// The fully unrolled one-wave build of those 16-lane shapes lives in lqmpc_r16_lat.hip and serves small batches.
 template <int NX, int NU, int N, int MODE, int LPI>
-struct R16Build {
-    static constexpr int OCC = ((LPI == 16 && N * NU > 10) || LPI == 64) ? 2 : 1;
-    // two waves per SIMD only where their LDS fits as well ((2,1,30): 33 KB per wavefront -> one wave, the whole register file)
-    static constexpr long long LDS_BYTES = (long long)(64 / LPI) * R16<NX, NU, N, LPI, (OCC == 2)>::INST * 8;
-    static constexpr int WAVES = ((OCC == 2 || (N * NU <= 10 && LPI == 16)) && LDS_BYTES * 8 <= 160 * 1024) ? 2 : 1;
-};
-
-template <int NX, int NU, int N, int MODE, int LPI>
-__global__ void __launch_bounds__(64, (R16Build<NX, NU, N, MODE, LPI>::WAVES)) lqmpc_r16_kernel(KParams p)
+__global__ void __launch_bounds__(64, (R16Build<NX, NU, N, LPI>::WAVES)) lqmpc_r16_kernel(KParams p)
 {
-    using C = R16<NX, NU, N, LPI, (R16Build<NX, NU, N, MODE, LPI>::OCC == 2)>;
+    using C = R16<NX, NU, N, LPI, (R16Build<NX, NU, N, LPI>::OCC == 2)>;
     __shared__ double lds_raw[C::IPW * C::INST];
-    r16_body<NX, NU, N, MODE, LPI, R16Build<NX, NU, N, MODE, LPI>::OCC>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
+    r16_body<NX, NU, N, MODE, LPI, R16Build<NX, NU, N, LPI>::OCC>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
 }
-
-struct R16Entry {
-    int nx, nu, N, lpi;
-    const char *name;
-    void (*launch)(const KParams &, hipStream_t);
-};
 
 template <int NX, int NU, int N, int LPI>
 static void launch_r16_one(const KParams &p, hipStream_t stream)
@@ -83,7 +67,7 @@ static void launch_r16_one(const KParams &p, hipStream_t stream)
 
 #define R16E(NX, NU, N) {NX, NU, N, 16, "lqmpc_r16_kernel<" #NX "," #NU "," #N ">", launch_r16_one<NX, NU, N, 16>}
 #define R64E(NX, NU, N) {NX, NU, N, 64, "lqmpc_r64_kernel<" #NX "," #NU "," #N ">", launch_r16_one<NX, NU, N, 64>}
-static const R16Entry g_r16[] = {
+static const ShapeEntry g_r16[] = {
     R16E(4, 2, 10),     // C3 (headline)
     R16E(2, 1, 10),     // C2
     R16E(2, 1, 5), R16E(2, 1, 6), R16E(2, 1, 7), R16E(2, 1, 8), R16E(2, 1, 9),   // C1 and the reference's horizon sweep
@@ -91,21 +75,19 @@ static const R16Entry g_r16[] = {
     R64E(4, 2, 20),     // C4 (n = 40): one instance per wavefront (LPI = 64), same algorithm, v_readlane broadcasts
 };
 
-bool launch_r16_lat(const KParams &p, hipStream_t stream);   // lqmpc_r16_lat.hip
-
-static const R16Entry *find_r16(int nx, int nu, int N)
+static const ShapeEntry *find_r16(int nx, int nu, int N)
 {
-    for (const R16Entry &e : g_r16)
+    for (const ShapeEntry &e : g_r16)
         if (e.nx == nx && e.nu == nu && e.N == N) return &e;
     return nullptr;
 }
 
 bool r16_available(int nx, int nu, int N) { return find_r16(nx, nu, N) != nullptr; }
-int r16_lanes(int nx, int nu, int N) { const R16Entry *e = find_r16(nx, nu, N); return e ? e->lpi : 0; }
+int r16_lanes(int nx, int nu, int N) { const ShapeEntry *e = find_r16(nx, nu, N); return e ? e->lpi : 0; }
 
 bool launch_r16(const KParams &p, hipStream_t stream, const char **name)
 {
-    const R16Entry *e = find_r16(p.nx, p.nu, p.N);
+    const ShapeEntry *e = find_r16(p.nx, p.nu, p.N);
     if (!e) return false;
     // a batch of at most one wave per SIMD: the latency build where the shape has one (lqmpc_r16_lat.hip)
     const bool lat = e->lpi == 16 && (p.r16_build >= 0 ? p.r16_build == 1 : p.Bsz <= 4096);

@@ -66,6 +66,17 @@ struct R16 {
     static_assert((n + 1) / 2 <= CS && n <= 64, "the smaller side must fit the gathered system");
 };
 
+// Register budget of a kernel around r16_body (one-shot, controller, run-time compiled): two waves per SIMD (256 registers) -- the
+// n <= 10 shapes as they are, the larger 16-lane shapes and the one-instance-per-wavefront mapping in the low-register build
+// (OCC = 2: rolled set-up loops, packed W, constants in LDS).  The fully unrolled one-wave build of those 16-lane shapes lives in
+// lqmpc_r16_lat.hip and serves small batches.
+template <int NX, int NU, int N, int LPI>
+struct R16Build {
+    static constexpr int OCC = ((LPI == 16 && N * NU > 10) || LPI == 64) ? 2 : 1;
+    // two waves per SIMD only where their LDS fits as well ((2,1,30): 33 KB per wavefront -> one wave, the whole register file)
+    static constexpr long long LDS_BYTES = (long long)(64 / LPI) * R16<NX, NU, N, LPI, (OCC == 2)>::INST * 8;
+    static constexpr int WAVES = ((OCC == 2 || (N * NU <= 10 && LPI == 16)) && LDS_BYTES * 8 <= 160 * 1024) ? 2 : 1;
+};
 
 // ---- the per-instance primitives in the two mappings ----
 // ballot over the lanes of my instance

@@ -5,6 +5,7 @@
 // size (launch_r16).  Same algorithm and iteration; the two builds differ in unrolling and in where the constants live.
 #include <cstdio>
 #include "lqmpc_r16_body.h"
+#include "lqmpc_launch.h"
 
 namespace lqmpc {
 

@@ -24,6 +24,7 @@
 #include "lqmpc_common.h"
 #include "lqmpc_r16_body.h"
 #include "lqmpc_probe.h"
+#include "lqmpc_launch.h"
 #include <cstdlib>
 
 #include <type_traits>

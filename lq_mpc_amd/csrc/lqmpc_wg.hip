@@ -27,6 +27,7 @@
 // part of the linear term qr = 2 gref + P centre (gref by a costate recursion on vectors) shifts the
 // unconstrained minimiser by v_r = -W qr.
 #include "lqmpc_wg_linalg.h"
+#include "lqmpc_launch.h"
 #include <cstdio>
 #include <type_traits>
 
@@ -89,11 +90,10 @@ __host__ __device__ inline WgOff wg_offsets(int nx, int nu, int N)
 
 size_t wg_lds_bytes(int nx, int nu, int N) { return (size_t)wg_offsets(nx, nu, N).total * sizeof(double) + 64; }
 
-bool wg_supported(const KParams &p, const double *lb, const double *ub)
+bool wg_supported(int nx, int nu, int N)
 {
-    (void)lb; (void)ub;
-    if (p.n <= 32 || p.n > 128 || p.nx > 16 || p.nu > 8) return false;      // (nx, nu: the closed-loop update lives in one wavefront)
-    const WgOff o = wg_offsets(p.nx, p.nu, p.N);
+    if (N * nu <= 32 || N * nu > 128 || nx > 16 || nu > 8) return false;      // (nx, nu: the closed-loop update lives in one wavefront)
+    const WgOff o = wg_offsets(nx, nu, N);
     return o.total <= LDS_DOUBLES && o.smax >= 1;
 }
 

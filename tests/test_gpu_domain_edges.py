@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the dispatch edges of lqmpc_api.hip:prepare() and degenerate boxes, against the long-double reference
+"""GPU (-m gpu): the dispatch edges of lqmpc_api.hip:make_plan() and degenerate boxes, against the long-double reference
 (oracle/exact.py) and the fp64 oracle.
 
 Bars against exact.py on these well-conditioned problems (spectral radius <= 1, SPD Q / R / P with condition <= 10):
@@ -249,7 +249,7 @@ def test_degenerate_boxes(solver, opts, shape, box):
     Bsz = 8192 + 3 if big else 67
     p = problem(nx, nu, N, Bsz, 3 * nx + N + len(box), lb, ub)
     # the big case rolls out on a shared plant with a centred box and no references: >= 8192 instances with T >= 4 order the
-    # walk by the clipped-roll key (lqmpc_api.hip prepare(): order_roll); elsewhere the plant is per instance
+    # walk by the clipped-roll key (lqmpc_api.hip make_plan(): order_roll); elsewhere the plant is per instance
     At, Bt = (p["A"][:, :, 0], p["B"][:, :, 0]) if big else (p["A"], p["B"])
     ht = lambda a, m: a if a.ndim == 2 else head(a, m)
     if box in ("positive", "negative"):
