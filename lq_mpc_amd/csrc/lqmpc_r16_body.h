@@ -1,5 +1,8 @@
-// lqmpc_r16_body.h -- device code of the 16-lane-row rollout (see lqmpc_r16.hip for the description);
-// shared by the stand-alone kernel there and by the tiered launch in lqmpc_spec.hip.
+// lqmpc_r16_body.h -- device code of the 16-lane-row layout: r16_body<NX, NU, N, MODE, LPI, OCC> is the whole kernel of one wavefront --
+// set-up on the matrix core (lqmpc_r16_setup.h), then the requested operation (MODE: one-shot solve, rollout, max V_N, fused sweep,
+// the prepared controller's factor and step) around qp(), one box QP by primal-dual active-set iterations.
+// Shared by the kernels of lqmpc_r16.hip (description of the layout there), lqmpc_r16_lat.hip and lqmpc_ctl.hip, by the wide tier of
+// lqmpc_spec.hip, and compiled at run time for the shapes without a prebuilt instantiation (lqmpc_jit.hip).
 #pragma once
 #include "lqmpc_wg_linalg.h"
 #include "lqmpc_r16_setup.h"
@@ -93,30 +96,7 @@ __device__ __forceinline__ double ibcast(double x, int k)
     if constexpr (LPI == 16) return rowb(x, k);
     else return wg::rdlane(x, k);
 }
-// acc += (lane k's x) * y
-template <int LPI>
-__device__ __forceinline__ void ifmac(double &acc, double x, double y, int k)
-{
-    if constexpr (LPI == 16) fmac_rowb(acc, x, y, k);
-    else acc = __builtin_fma(wg::rdlane(x, k), y, acc);
-}
-// acc += (lane k's acc) * y
-template <int LPI>
-__device__ __forceinline__ void ifmac_self(double &acc, double y, int k)
-{
-    if constexpr (LPI == 16) fmac_rowb_self(acc, y, k);
-    else acc = __builtin_fma(wg::rdlane(acc, k), y, acc);
-}
-// four of each with one lane and one multiplier
-template <int LPI>
-__device__ __forceinline__ void ifmac4(double *acc, const double *x, double y, int k)
-{
-    if constexpr (LPI == 16) fmac_rowb4(acc[0], acc[1], acc[2], acc[3], x[0], x[1], x[2], x[3], y, k);
-    else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = __builtin_fma(wg::rdlane(x[e], k), y, acc[e]);
-    }
-}
+// acc[0..3] += (lane k's acc[0..3]) * y: four self-updates with one lane and one multiplier
 template <int LPI>
 __device__ __forceinline__ void ifmac_self4(double *acc, double y, int k)
 {
@@ -175,10 +155,6 @@ __device__ __forceinline__ unsigned row_umax(unsigned x)
     x = max(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x121, 0xF, 0xF, false));
     return x;
 }
-
-// compile-time loop: f(ic<0>{}) ... f(ic<CNT - 1>{})
-template <int CNT, typename F>
-__device__ __forceinline__ void static_for(F &&f) { sfor<0, CNT>(f); }
 
 // OCC = 2: built for two waves per SIMD (256 registers): the horizon loops of the condensing stay rolled and the stage weights
 // and the plant live in LDS instead of registers (they are the loop-invariant values the allocator would otherwise reload
@@ -275,6 +251,8 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
         // Set-up on the matrix core (lqmpc_r16_setup.h): Riccati recursion, W by rank-NU tile updates, G from the same sweep, P from
         // its Toeplitz form -- v_mfma_f64_4x4x4_4b_f64 products only.  MFMA block g = (lane >> 2) & 3 works for the instance of lanes
         // 16g .. 16g+15 (LPI = 16), so the set-up takes its inputs and its LDS by g and hands G back through LDS.
+        // (The same lookup stands once more before the lazy build of P in qp(): as a function, free or local, it reorders register
+        // copies in three one-shot kernels -- profiles/r16_iter_split_attempts.txt.)
         RPROF_START;
         long long bg = b;
         ldsd *Lg = L;
@@ -573,12 +551,12 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                             else return ta + lb;
                         };
                         double S[CS];
-                        static_for<CS / 4>([&](auto bgc) {
+                        sfor<0, CS / 4>([&](auto bgc) {
                             constexpr int bg = decltype(bgc)::value;
 #pragma unroll
                             for (int bb = 4 * bg; bb < 4 * bg + 4; ++bb) S[bb] = (bb == i) ? 1.0 : 0.0;
                             if (4 * bg < cw) {                                   // uniform
-                                static_for<4>([&](auto bc) {
+                                sfor<0, 4>([&](auto bc) {
                                     constexpr int bb = 4 * bg + decltype(bc)::value;
                                     const int lb = rowb_i(la, bb), tlb = PACKED ? rowb_i(tla, bb) : 0;
                                     const double val = Wp[widx(la, tla, lb, tlb)];
@@ -587,7 +565,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                             }
                         });
                         bool ok = true;
-                        static_for<CS>([&](auto kc) {
+                        sfor<0, CS>([&](auto kc) {
                             constexpr int k = decltype(kc)::value;
                             if (k < cw) {
                                 isettle<LPI>(S[k]);
@@ -607,11 +585,11 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
 #pragma unroll
                         for (int s = 0; s < RB; ++s) tt[s] = 0.0;
                         const int trow[2] = {PACKED ? tri[0] : rw[0] * LDW, RB > 1 ? (PACKED ? tri[RB - 1] : rw[RB - 1] * LDW) : 0};
-                        static_for<CS / 4>([&](auto kgc) {
+                        sfor<0, CS / 4>([&](auto kgc) {
                             constexpr int kg = decltype(kgc)::value;
                             if (4 * kg < cw) {                                   // uniform
                                 double wv[4][RB];
-                                static_for<4>([&](auto kc) {
+                                sfor<0, 4>([&](auto kc) {
                                     constexpr int kk = decltype(kc)::value;
                                     const int lk = rowb_i(la, 4 * kg + kk), tlk = PACKED ? rowb_i(tla, 4 * kg + kk) : 0;
 #pragma unroll
@@ -620,7 +598,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                                 if constexpr (RB == 2) fmac_rowb_lanes4x2(tt[0], tt[1], rhs, wv[0][0], wv[0][1], wv[1][0], wv[1][1], wv[2][0], wv[2][1], wv[3][0], wv[3][1], 4 * kg);
                                 else if constexpr (RB == 1) fmac_rowb_lanes4(tt[0], rhs, wv[0][0], wv[1][0], wv[2][0], wv[3][0], 4 * kg);
                                 else {
-                                    static_for<4>([&](auto kc) {
+                                    sfor<0, 4>([&](auto kc) {
                                         constexpr int kk = decltype(kc)::value;
 #pragma unroll
                                         for (int s = 0; s < RB; ++s) fmac_rowb(tt[s], rhs, wv[kk][s], 4 * kg + kk);
@@ -704,12 +682,12 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                             else return ta + lb;
                         };
                         double S[CS];
-                        static_for<CS / 4>([&](auto bgc) {
+                        sfor<0, CS / 4>([&](auto bgc) {
                             constexpr int bg = decltype(bgc)::value;
 #pragma unroll
                             for (int bb = 4 * bg; bb < 4 * bg + 4; ++bb) S[bb] = (bb == i) ? 1.0 : 0.0;
                             if (4 * bg < cw) {
-                                static_for<4>([&](auto bc) {
+                                sfor<0, 4>([&](auto bc) {
                                     constexpr int bb = 4 * bg + decltype(bc)::value;
                                     const int lb = rowb_i(la, bb), tlb = PACKED ? rowb_i(tla, bb) : 0;
                                     const double val = Mx[midx(la, tla, lb, tlb)];
@@ -718,7 +696,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                             }
                         });
                         bool ok = true;
-                        static_for<CS>([&](auto kc) {
+                        sfor<0, CS>([&](auto kc) {
                             constexpr int k = decltype(kc)::value;
                             if (k < cw) {
                                 isettle<LPI>(S[k]);
@@ -738,11 +716,11 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
 #pragma unroll
                         for (int s = 0; s < RB; ++s) tt[s] = 0.0;
                         const int trow[2] = {PACKED ? tri[0] : rw[0] * LDW, RB > 1 ? (PACKED ? tri[RB - 1] : rw[RB - 1] * LDW) : 0};
-                        static_for<CS / 4>([&](auto kgc) {
+                        sfor<0, CS / 4>([&](auto kgc) {
                             constexpr int kg = decltype(kgc)::value;
                             if (4 * kg < cw) {
                                 double wv[4][RB];
-                                static_for<4>([&](auto kc) {
+                                sfor<0, 4>([&](auto kc) {
                                     constexpr int kk = decltype(kc)::value;
                                     const int lk = rowb_i(la, 4 * kg + kk), tlk = PACKED ? rowb_i(tla, 4 * kg + kk) : 0;
 #pragma unroll
@@ -751,7 +729,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                                 if constexpr (RB == 2) fmac_rowb_lanes4x2(tt[0], tt[1], rhs, wv[0][0], wv[0][1], wv[1][0], wv[1][1], wv[2][0], wv[2][1], wv[3][0], wv[3][1], 4 * kg);
                                 else if constexpr (RB == 1) fmac_rowb_lanes4(tt[0], rhs, wv[0][0], wv[1][0], wv[2][0], wv[3][0], 4 * kg);
                                 else {
-                                    static_for<4>([&](auto kc) {
+                                    sfor<0, 4>([&](auto kc) {
                                         constexpr int kk = decltype(kc)::value;
 #pragma unroll
                                         for (int s = 0; s < RB; ++s) fmac_rowb(tt[s], rhs, wv[kk][s], 4 * kg + kk);
@@ -827,12 +805,12 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                         else return ta + lb;
                     };
                     double S[CS];
-                    static_for<CS / 4>([&](auto bgc) {
+                    sfor<0, CS / 4>([&](auto bgc) {
                         constexpr int bg = decltype(bgc)::value;
 #pragma unroll
                         for (int bb = 4 * bg; bb < 4 * bg + 4; ++bb) S[bb] = (bb == i) ? 1.0 : 0.0;
                         if (4 * bg < cw) {
-                            static_for<4>([&](auto bc) {
+                            sfor<0, 4>([&](auto bc) {
                                 constexpr int bb = 4 * bg + decltype(bc)::value;
                                 const int lb = __builtin_amdgcn_readlane(la, bb), tlb = PACKED ? __builtin_amdgcn_readlane(tla, bb) : 0;
                                 const double val = Wp[widx(la, tla, lb, tlb)];
@@ -841,7 +819,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                         }
                     });
                     bool ok = true;
-                    static_for<CS>([&](auto kc) {
+                    sfor<0, CS>([&](auto kc) {
                         constexpr int k = decltype(kc)::value;
                         if (k < cw) {
                             const double d = ibcast<LPI>(S[k], k);
@@ -860,7 +838,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                     const int trow0 = PACKED ? tri[0] : rw[0] * LDW;
                     unsigned smax = 0u;
                     const unsigned lhi = (unsigned)__double2hiint(rhs) & 0x7fffffffu;
-                    static_for<CS>([&](auto kc) {
+                    sfor<0, CS>([&](auto kc) {
                         constexpr int k = decltype(kc)::value;
                         if (k < cw) {
                             const int lk = __builtin_amdgcn_readlane(la, k), tlk = PACKED ? __builtin_amdgcn_readlane(tla, k) : 0;
@@ -873,7 +851,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                     const bool isL = (mL >> la) & 1ull;
                     const mask_t kL = __ballot(mine && isL && rhs <= tol), kU = __ballot(mine && !isL && rhs >= -tol);   // by unknown k
                     mask_t nL = 0, nU = 0;
-                    static_for<CS>([&](auto kc) {
+                    sfor<0, CS>([&](auto kc) {
                         constexpr int k = decltype(kc)::value;
                         if (k < cw) {
                             const int lk = __builtin_amdgcn_readlane(la, k);
@@ -905,39 +883,22 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                     if (__ballot(busy) == 0ull) break;
                     continue;
                 }
-                // publish v_unc, r = v_unc - s h on the active rows (0 elsewhere), the list of the chosen side
+                // ---- one instance per wavefront, the general path: the only one of that mapping that can take the primal side.  Both
+                // four-instance branches and the dual branch above end in `continue`: what follows is reached with LPI = 64 only ----
+                if constexpr (LPI == 64) {
+                    // publish v_unc, r = v_unc - s h on the active rows (0 elsewhere), the list of the chosen side
 #pragma unroll
-                for (int s = 0; s < RB; ++s) {
-                    const mask_t bit = 1ull << rw[s];
-                    const double sg = (mL & bit) ? -1.0 : ((mU & bit) ? 1.0 : 0.0);
-                    rL[rw[s]] = (sg != 0.0) ? vu[s] - sg * h[s] : 0.0;
-                    xL[rw[s]] = 0.0;
-                    if (vrow[s] && (mC & bit)) list[__popcll(mC & (bit - 1ull))] = rw[s];
-                }
-                __syncthreads();
-                const ldsd *Mx = dual ? Wp : Pp;
-                const int la = (i < c) ? list[i] : 0, tla = la * (la + 1) / 2;
-                double S[CS], rhs;
-                if constexpr (LPI == 16) {
-                    // the column indices reach the lanes as DPP broadcasts of la: no dependent LDS reads, every load of a group in flight
-                    // at once.  Only lanes without an unknown need the identity: columns beyond c meet zeros only (see the dual-only path).
-                    const int tla2 = PACKED ? tla : la * LDW;
-                    static_for<CS / 4>([&](auto bgc) {
-                        constexpr int bg = decltype(bgc)::value;
-#pragma unroll
-                        for (int bb = 4 * bg; bb < 4 * bg + 4; ++bb) S[bb] = (bb == i) ? 1.0 : 0.0;
-                        if (4 * bg < cw) {
-                            static_for<4>([&](auto bc) {
-                                constexpr int bb = 4 * bg + decltype(bc)::value;
-                                const int lb = rowb_i(la, bb), tlb = PACKED ? rowb_i(tla2, bb) : 0;
-                                int idx;
-                                if constexpr (PACKED) idx = max(tla2, tlb) + min(la, lb); else idx = tla2 + lb;
-                                const double val = Mx[idx];
-                                S[bb] = (i < c) ? val : S[bb];
-                            });
-                        }
-                    });
-                } else {
+                    for (int s = 0; s < RB; ++s) {
+                        const mask_t bit = 1ull << rw[s];
+                        const double sg = (mL & bit) ? -1.0 : ((mU & bit) ? 1.0 : 0.0);
+                        rL[rw[s]] = (sg != 0.0) ? vu[s] - sg * h[s] : 0.0;
+                        xL[rw[s]] = 0.0;
+                        if (vrow[s] && (mC & bit)) list[__popcll(mC & (bit - 1ull))] = rw[s];
+                    }
+                    __syncthreads();
+                    const ldsd *Mx = dual ? Wp : Pp;
+                    const int la = (i < c) ? list[i] : 0, tla = la * (la + 1) / 2;
+                    double S[CS], rhs;
 #pragma unroll
                     for (int bg = 0; bg < CS / 4; ++bg) {            // columns in groups of four: one uniform test per group
 #pragma unroll
@@ -951,86 +912,86 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                             }
                         }
                     }
-                }
-                rhs = (i < c && dual) ? rL[la] : 0.0;
-                if (any_primal) {
-                    double tp = 0.0;
+                    rhs = (i < c && dual) ? rL[la] : 0.0;
+                    if (any_primal) {
+                        double tp = 0.0;
 #pragma unroll
-                    for (int j = 0; j < n; ++j) tp = __builtin_fma(Pp[ad(la, tla, j)], rL[j], tp);
-                    if (i < c && !dual) rhs = tp;
-                }
-                // Gauss-Jordan on [S | rhs]: afterwards S = I and rhs = the solution
-                bool ok = true;
-                static_for<CS>([&](auto kc) {                    // (compile-time pivot index: the DPP control is an immediate)
-                    constexpr int k = decltype(kc)::value;
-                    if (k < cw) {                                // uniform
-                        isettle<LPI>(S[k]);
-                        const double d = ibcast<LPI>(S[k], k);
-                        ok = ok && (d > 0.0);
-                        const double inv = frcp1(d);
-                        const double g = (i == k) ? (inv - 1.0) : -S[k] * inv;
-#pragma unroll
-                        for (int jg = 0; jg < CS / 4; ++jg)      // columns in groups of four: one uniform test per group (first half static)
-                            if (4 * jg > k && 4 * jg < cw) ifmac_self4<LPI>(&S[4 * jg], g, k);
-                        ifmac_self_tail<LPI, k>(S, rhs, g);
+                        for (int j = 0; j < n; ++j) tp = __builtin_fma(Pp[ad(la, tla, j)], rL[j], tp);
+                        if (i < c && !dual) rhs = tp;
                     }
-                });
-                const bool rowfail = iballot<LPI>(!ok, q) != 0;
-                if (i < c) xL[la] = rhs;
-                __syncthreads();
-                double xs_[RB];
+                    // Gauss-Jordan on [S | rhs]: afterwards S = I and rhs = the solution
+                    bool ok = true;
+                    sfor<0, CS>([&](auto kc) {                    // (compile-time pivot index: the DPP control is an immediate)
+                        constexpr int k = decltype(kc)::value;
+                        if (k < cw) {                                // uniform
+                            isettle<LPI>(S[k]);
+                            const double d = ibcast<LPI>(S[k], k);
+                            ok = ok && (d > 0.0);
+                            const double inv = frcp1(d);
+                            const double g = (i == k) ? (inv - 1.0) : -S[k] * inv;
 #pragma unroll
-                for (int s = 0; s < RB; ++s) {                   // y = x (dual side) or x - r (primal side): what the matrix row multiplies
-                    xs_[s] = xL[rw[s]];
-                    yL[rw[s]] = dual ? xs_[s] : xs_[s] - rL[rw[s]];
-                }
-                __syncthreads();
-                // t = (M y)_row with y = x (dual, M = W) or x - r (primal, M = P); x is zero off the chosen side
-                double tol = 0.0, gl[RB];
+                            for (int jg = 0; jg < CS / 4; ++jg)      // columns in groups of four: one uniform test per group (first half static)
+                                if (4 * jg > k && 4 * jg < cw) ifmac_self4<LPI>(&S[4 * jg], g, k);
+                            ifmac_self_tail<LPI, k>(S, rhs, g);
+                        }
+                    });
+                    const bool rowfail = iballot<LPI>(!ok, q) != 0;
+                    if (i < c) xL[la] = rhs;
+                    __syncthreads();
+                    double xs_[RB];
 #pragma unroll
-                for (int s = 0; s < RB; ++s) {
-                    double tt = 0.0;
-                    const int mr = vrow[s] ? rw[s] : 0, mt = vrow[s] ? tri[s] : 0;
+                    for (int s = 0; s < RB; ++s) {                   // y = x (dual side) or x - r (primal side): what the matrix row multiplies
+                        xs_[s] = xL[rw[s]];
+                        yL[rw[s]] = dual ? xs_[s] : xs_[s] - rL[rw[s]];
+                    }
+                    __syncthreads();
+                    // t = (M y)_row with y = x (dual, M = W) or x - r (primal, M = P); x is zero off the chosen side
+                    double tol = 0.0, gl[RB];
 #pragma unroll
-                    for (int j = 0; j < n; ++j) tt = __builtin_fma(Mx[ad(mr, mt, j)], yL[j], tt);
-                    const mask_t bit = 1ull << rw[s];
-                    const bool act = vrow[s] && (mA & bit);
-                    const double sg = (mL & bit) ? -1.0 : 1.0;
-                    const double xs = xs_[s];
-                    // free rows: the new value; active rows: the bound, and the gradient there (rows that are done keep theirs)
-                    const double nv = act ? sg * h[s] : (dual ? vu[s] - tt : vu[s] + xs);
-                    v[s] = busy ? nv : v[s];
-                    gl[s] = act ? (dual ? -xs : tt) : 0.0;
-                    tol = fmax(tol, fabs(gl[s]));
-                }
-                tol = fmax(tol, __shfl_xor(tol, 1)); tol = fmax(tol, __shfl_xor(tol, 2));
-                tol = fmax(tol, __shfl_xor(tol, 4)); tol = fmax(tol, __shfl_xor(tol, 8));
-                if (LPI == 64) { tol = fmax(tol, __shfl_xor(tol, 16)); tol = fmax(tol, __shfl_xor(tol, 32)); }
-                tol *= 1e-10;
-                mask_t nL = 0, nU = 0;
-                bool nf = false;
+                    for (int s = 0; s < RB; ++s) {
+                        double tt = 0.0;
+                        const int mr = vrow[s] ? rw[s] : 0, mt = vrow[s] ? tri[s] : 0;
 #pragma unroll
-                for (int s = 0; s < RB; ++s) {
-                    const mask_t bit = 1ull << rw[s];
-                    const bool act = vrow[s] && (mA & bit);
-                    const bool lo = act ? ((mL & bit) && gl[s] >= -tol) : (vrow[s] && v[s] < -h[s] * (1.0 + 1e-12));
-                    const bool up = act ? ((mU & bit) && gl[s] <= tol) : (vrow[s] && v[s] > h[s] * (1.0 + 1e-12));
-                    nL |= iballot<LPI>(lo, q) << (LPI * s);
-                    nU |= iballot<LPI>(up, q) << (LPI * s);
-                    nf = nf || (vrow[s] && !(fabs(v[s]) < 1e300));
-                }
-                const bool rownf = iballot<LPI>(nf, q) != 0;
+                        for (int j = 0; j < n; ++j) tt = __builtin_fma(Mx[ad(mr, mt, j)], yL[j], tt);
+                        const mask_t bit = 1ull << rw[s];
+                        const bool act = vrow[s] && (mA & bit);
+                        const double sg = (mL & bit) ? -1.0 : 1.0;
+                        const double xs = xs_[s];
+                        // free rows: the new value; active rows: the bound, and the gradient there (rows that are done keep theirs)
+                        const double nv = act ? sg * h[s] : (dual ? vu[s] - tt : vu[s] + xs);
+                        v[s] = busy ? nv : v[s];
+                        gl[s] = act ? (dual ? -xs : tt) : 0.0;
+                        tol = fmax(tol, fabs(gl[s]));
+                    }
+                    tol = fmax(tol, __shfl_xor(tol, 1)); tol = fmax(tol, __shfl_xor(tol, 2));
+                    tol = fmax(tol, __shfl_xor(tol, 4)); tol = fmax(tol, __shfl_xor(tol, 8));
+                    tol = fmax(tol, __shfl_xor(tol, 16)); tol = fmax(tol, __shfl_xor(tol, 32));
+                    tol *= 1e-10;
+                    mask_t nL = 0, nU = 0;
+                    bool nf = false;
+#pragma unroll
+                    for (int s = 0; s < RB; ++s) {
+                        const mask_t bit = 1ull << rw[s];
+                        const bool act = vrow[s] && (mA & bit);
+                        const bool lo = act ? ((mL & bit) && gl[s] >= -tol) : (vrow[s] && v[s] < -h[s] * (1.0 + 1e-12));
+                        const bool up = act ? ((mU & bit) && gl[s] <= tol) : (vrow[s] && v[s] > h[s] * (1.0 + 1e-12));
+                        nL |= iballot<LPI>(lo, q) << (LPI * s);
+                        nU |= iballot<LPI>(up, q) << (LPI * s);
+                        nf = nf || (vrow[s] && !(fabs(v[s]) < 1e300));
+                    }
+                    const bool rownf = iballot<LPI>(nf, q) != 0;
 #ifdef LQMPC_R16_PROF
-                prof_wit += 1; prof_slow += 1; prof_slowt += clock64() - prof_it0;
+                    prof_wit += 1; prof_slow += 1; prof_slowt += clock64() - prof_it0;
 #endif
-                if (busy) {
-                    iters += 1;
-                    if (rowfail || rownf) { failed = true; busy = false; }
-                    else if (nL == mL && nU == mU) busy = false;
-                    else { mL = nL; mU = nU; }
+                    if (busy) {
+                        iters += 1;
+                        if (rowfail || rownf) { failed = true; busy = false; }
+                        else if (nL == mL && nU == mU) busy = false;
+                        else { mL = nL; mU = nU; }
+                    }
+                    __syncthreads();
+                    if (__ballot(busy) == 0ull) break;
                 }
-                __syncthreads();
-                if (__ballot(busy) == 0ull) break;
             }
         }
         } while (LAZY_P && need_P);
