@@ -135,7 +135,10 @@ typedef struct lqmpc_options {
     int32_t jit;        /* shapes (nx, nu, N) without a prebuilt instantiation: compile the 16-lane-row kernel for them at run time
                           (hiprtc; nx <= 8, nu <= 4, N*nu <= 48; about two seconds per shape and entry point on first use, then
                           cached) instead of falling back to the generic kernel.  -1 auto (= on), 0 off, 1 on.  (default -1) */
-    int32_t reserved2;  /* 0 */
+    int32_t ctl_wg;     /* prepared controllers (lqmpc_controller_*) on the workgroup kernel's shapes: 0 every step is
+                          lqmpc_solve_batch_dev (pass-through), 1 a controller created while this is set keeps one record per
+                          instance there as well (kernel AUTO or WORKGROUP, presolve and warm start not switched off).  Opt-in
+                          because of the memory: about 166 KB per instance at (8,4,30).  (default 0; the slot was reserved2) */
 } lqmpc_options;
 
 /* Limits of this build. */
@@ -282,10 +285,13 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
  * state x; as it is when the state did not advance (the same state asked again).  It never decides the answer.
  *
  * The controller takes a snapshot of the handle's options when it is created (eps, max_iter, r16_maxit, presolve, warm_start,
- * kernel, layout, jit) and uses the handle's device, stream and scratch; later lqmpc_set_options calls do not reach it.  The record
+ * kernel, layout, jit, ctl_wg) and uses the handle's device, stream and scratch; later lqmpc_set_options calls do not reach it.  The record
  * kernels serve exactly the shapes and options for which lqmpc_solve_batch runs the 16-lane-row family (prebuilt or run-time
- * compiled); everywhere else the controller keeps device copies of A and B and every step is lqmpc_solve_batch_dev on them, so the
- * interface covers the library's whole domain.  Destroy every controller BEFORE its handle.  Not thread-safe (as the handle).
+ * compiled).  With options.ctl_wg = 1 they also serve the shapes on which it runs the workgroup kernel (32 < N nu <= 128): there a
+ * record is [A | B | G | v_r] and then W and P as the block images the kernel works on, a step is one launch of
+ * lqmpc_wg_ctl_step_kernel, and W and P are read only by the instances that have to iterate.  Everywhere else the controller keeps
+ * device copies of A and B and every step is lqmpc_solve_batch_dev on them, so the interface covers the library's whole domain.
+ * Destroy every controller BEFORE its handle.  Not thread-safe (as the handle).
  *
  * create: A, B per instance (instance-minor; host for _create, device for _create_dev), Q, R, P, lb, ub, x_ref, u_ref HOST (the
  *   references may be NULL).  Same argument checks and error codes as lqmpc_solve_batch.  Everything is copied: the caller may free

@@ -40,7 +40,7 @@ class Options(ctypes.Structure):
                 ("max_iter", ctypes.c_int32), ("polish", ctypes.c_int32), ("kernel", ctypes.c_int32),
                 ("presolve", ctypes.c_int32), ("order", ctypes.c_int32), ("warm_start", ctypes.c_int32),
                 ("layout", ctypes.c_int32), ("r16_maxit", ctypes.c_int32), ("r16_build", ctypes.c_int32),
-                ("nwide", ctypes.c_int32), ("jit", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
+                ("nwide", ctypes.c_int32), ("jit", ctypes.c_int32), ("ctl_wg", ctypes.c_int32)]
 
 
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_SPECIALIZED, KERNEL_WORKGROUP = 0, 1, 2, 3

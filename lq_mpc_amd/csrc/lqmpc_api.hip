@@ -142,7 +142,7 @@ void lqmpc_default_options(lqmpc_options *opt)
     opt->r16_build = -1;
     opt->nwide = -1;
     opt->jit = -1;
-    opt->reserved2 = 0;
+    opt->ctl_wg = 0;
 }
 
 int lqmpc_create_on_stream(int device, void *hip_stream, lqmpc_handle **out)
@@ -224,6 +224,7 @@ int lqmpc_set_options(lqmpc_handle *h, const lqmpc_options *opt)
     if (opt->r16_build < -1 || opt->r16_build > 1) return fail(LQMPC_ERR_BAD_ARG, "r16_build must be -1, 0 or 1");
     if (opt->nwide < -1) return fail(LQMPC_ERR_BAD_ARG, "nwide must be -1 (auto) or a count");
     if (opt->jit < -1 || opt->jit > 1) return fail(LQMPC_ERR_BAD_ARG, "jit must be -1, 0 or 1");
+    if (opt->ctl_wg < 0 || opt->ctl_wg > 1) return fail(LQMPC_ERR_BAD_ARG, "ctl_wg must be 0 or 1");
     h->opt = *opt;
     return 0;
 }
@@ -1156,6 +1157,7 @@ struct lqmpc_controller {
     void *vn = nullptr;                       // V_N of a step whose caller passed NULL (the solve kernels always write it); on first need
     size_t bytes = 0;
     bool fast = false, jit = false;           // fast: the record kernels serve the shape (jit: compiled at run time); else pass-through
+    bool wg = false;                          // fast, on the workgroup kernel's shapes (options.ctl_wg): one launch per step, no hand-back
     std::string name = "lqmpc_solve_batch_dev";
 };
 
@@ -1187,6 +1189,8 @@ int ctl_launch(lqmpc_controller *c, const KParams &p)
     if (c->jit) {
         std::string why;
         if (!lqmpc::launch_jit(h->device, p, h->stream, nullptr, &why)) return fail(LQMPC_ERR_HIP, "run-time compiled controller kernel: " + why);
+    } else if (c->wg) {
+        if (!lqmpc::launch_wg_ctl(p, h->stream, nullptr)) return fail(LQMPC_ERR_HIP, "workgroup controller kernel launch failed");
     } else if (!lqmpc::launch_ctl(p, h->stream, nullptr)) return fail(LQMPC_ERR_UNSUPPORTED, "controller kernel launch failed");
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1196,7 +1200,7 @@ void ctl_bind(const lqmpc_controller *c, KParams &p)
 {
     p.A = (const double *)c->A; p.B = (const double *)c->B;
     p.ctl_rec = (double *)c->rec;
-    p.ctl_stride = lqmpc::ctl_rec_layout(c->nx, c->nu, c->N).stride;
+    p.ctl_stride = c->wg ? lqmpc::wg_ctl_rec_layout(c->nx, c->nu, c->N).stride : lqmpc::ctl_rec_layout(c->nx, c->nu, c->N).stride;
     p.ctl_face = (unsigned long long *)c->face;
 }
 
@@ -1227,24 +1231,29 @@ int ctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double
                                lqmpc::jit_available(h->device, nx, nu, N, lqmpc::MODE_CTL_STEP, &why);
             if (!c->fast) g_err = "run-time compile unavailable, the controller passes through to lqmpc_solve_batch_dev: " + why;
         }
+    } else if (h->opt.ctl_wg == 1 && pl.family == FAM_WG && p.presolve && p.warm_start) {
+        // opt-in (a record is two images of the block triangle: 166 KB per instance at (8,4,30)): records on the workgroup kernel's shapes
+        c->fast = c->wg = true;
     }
+    const size_t face_words = c->wg ? (size_t)(lqmpc::WG_CTL_FACE_WORDS + 2 * nx) : (size_t)(2 + 2 * nx);
+    const size_t rec_doubles = c->wg ? (size_t)lqmpc::wg_ctl_rec_layout(nx, nu, N).stride : (size_t)lqmpc::ctl_rec_layout(nx, nu, N).stride;
     const size_t b = (size_t)Bsz, nA = b * nx * nx * sizeof(double), nB = b * nx * nu * sizeof(double);
     rc = ctl_alloc(c, &c->A, nA);
     if (!rc) rc = ctl_alloc(c, &c->B, nB);
     if (!rc && c->fast) {
-        rc = ctl_alloc(c, &c->rec, b * (size_t)lqmpc::ctl_rec_layout(nx, nu, N).stride * sizeof(double));
-        if (!rc) rc = ctl_alloc(c, &c->face, b * (size_t)(2 + 2 * nx) * sizeof(unsigned long long));
+        rc = ctl_alloc(c, &c->rec, b * rec_doubles * sizeof(double));
+        if (!rc) rc = ctl_alloc(c, &c->face, b * face_words * sizeof(unsigned long long));
     }
     if (rc) { ctl_free(c); return rc; }
     hipError_t e = hipMemcpyAsync(c->A, A, nA, kind, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->B, B, nB, kind, h->stream);
-    if (e == hipSuccess && c->fast) e = hipMemsetAsync(c->face, 0, b * (size_t)(2 + 2 * nx) * sizeof(unsigned long long), h->stream);
+    if (e == hipSuccess && c->fast) e = hipMemsetAsync(c->face, 0, b * face_words * sizeof(unsigned long long), h->stream);
     if (e != hipSuccess) { ctl_free(c); return fail(LQMPC_ERR_HIP, std::string("controller copy: ") + hipGetErrorString(e)); }
     if (c->fast) {
         char nm[96];
         snprintf(nm, sizeof nm, "lqmpc_ctl_r%d%s_kernel<%d,%d,%d>", N * nu <= 32 ? 16 : 64, c->jit ? "_jit" : "", nx, nu, N);
         if (!c->jit && lqmpc::r16_lanes(nx, nu, N) == 64) snprintf(nm, sizeof nm, "lqmpc_ctl_r64_kernel<%d,%d,%d>", nx, nu, N);
-        c->name = nm;
+        c->name = c->wg ? "lqmpc_wg_ctl_step_kernel" : nm;
         ctl_bind(c, p);
         p.mode = lqmpc::MODE_CTL_FACTOR;
         rc = ctl_launch(c, p);
@@ -1253,6 +1262,12 @@ int ctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double
     // the caller may overwrite A and B as soon as this returns
     e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) { ctl_free(c); return fail(LQMPC_ERR_HIP, std::string("controller set-up: ") + hipGetErrorString(e)); }
+    if (c->wg) {
+        // the records hold A and B, and nothing is handed back to a kernel that would read the copies
+        (void)hipFree(c->A); (void)hipFree(c->B);
+        c->A = c->B = nullptr;
+        c->bytes -= nA + nB;
+    }
     *out = c;
     return 0;
 }
@@ -1294,9 +1309,15 @@ int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0
     if (rc) return rc;
     ctl_bind(c, p);
     p.x0 = dx; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
+    p.mode = lqmpc::MODE_CTL_STEP;
+    if (c->wg) {
+        // one launch: the workgroup kernel's fall-back (interior point on the n x n matrices) is inside solve_qp
+        rc = ctl_launch(c, p);
+        if (!rc) h->last_kernel = c->name.c_str();
+        return rc;
+    }
     rc = prepare_hand_back(h, p);
     if (rc) return rc;
-    p.mode = lqmpc::MODE_CTL_STEP;
     rc = ctl_launch(c, p);
     if (rc) return rc;
     // whatever did not settle within r16_maxit iterations (or arrived with a non-finite state): the existing kernels, from scratch, over
@@ -1332,7 +1353,8 @@ int lqmpc_controller_reset(lqmpc_controller *c)
     if (!c) return fail(LQMPC_ERR_BAD_ARG, "controller is NULL");
     if (!c->face) return 0;
     HIP_TRY(hipSetDevice(c->h->device));
-    HIP_TRY(hipMemsetAsync(c->face, 0, (size_t)c->Bsz * (size_t)(2 + 2 * c->nx) * sizeof(unsigned long long), c->h->stream));
+    const size_t words = c->wg ? (size_t)(lqmpc::WG_CTL_FACE_WORDS + 2 * c->nx) : (size_t)(2 + 2 * c->nx);
+    HIP_TRY(hipMemsetAsync(c->face, 0, (size_t)c->Bsz * words * sizeof(unsigned long long), c->h->stream));
     return 0;
 }
 

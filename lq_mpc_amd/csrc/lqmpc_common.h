@@ -81,7 +81,23 @@ struct CtlRecT {
     static constexpr int oA = L.oA, oB = L.oB, oG = L.oG, oV = L.oV, oW = L.oW, oP = L.oP, tri = L.tri, stride = L.stride;
 };
 
-constexpr int ORDER_BUCKETS = 512;           // difficulty buckets of the ordering: 16 per binade of the key over [2^-2, 2^30)
+// One record of a prepared controller on the workgroup kernel's shapes (lqmpc_wg.hip), in doubles: [A | B | G (np x nx, column-major) |
+// v_r (np)] (what every step reads), then [W] and [P] (what only an instance that has to iterate reads): the lower block triangle of
+// 16 x 16 blocks exactly as it lies in LDS / in the registers (nb (nb + 1) / 2 blocks of 16 rows x 17 doubles, element e = t + 256 m
+// belongs to thread t), so that storing and loading it is a flat, fully coalesced copy.  n = N nu, nb = ceil(n / 16), np = 16 nb.
+// W starts on a 256-byte boundary; the stride is padded to 256 bytes.
+struct WgCtlRec {
+    int oA, oB, oG, oV, oW, oP, img, stride;
+};
+__host__ __device__ constexpr WgCtlRec wg_ctl_rec_layout(int nx, int nu, int N)
+{
+    const int n = N * nu, nb = (n + 15) / 16, np = nb * 16, img = nb * (nb + 1) / 2 * (16 * 17);
+    const int oB = nx * nx, oG = oB + nx * nu, oV = oG + np * nx, oW = (oV + np + 31) / 32 * 32, oP = oW + img;
+    return WgCtlRec{0, oB, oG, oV, oW, oP, img, (oP + img + 31) / 32 * 32};
+}
+constexpr int WG_CTL_FACE_WORDS = 4;         // per instance in front of the two states: (lower, upper) row masks of rows 0..63, then of rows 64..127
+
+constexpr int ORDER_BUCKETS = 512;          // difficulty buckets of the ordering: 16 per binade of the key over [2^-2, 2^30)
 constexpr int ORDER_COPIES = 8;              // counters per bucket (wavefront w uses copy w % 8): spreads the atomics on a popular bucket
 constexpr int ORDER_CELLS = ORDER_BUCKETS * ORDER_COPIES;
 constexpr int ORDER_PAD = 16;                // ints between two counters: one 64-byte line each (atomics on one line serialise)

@@ -36,6 +36,8 @@ bool launch_r16_lat(const KParams &p, hipStream_t stream);
 // lqmpc_wg.hip: one instance per workgroup, 32 < n <= 128
 bool wg_supported(int nx, int nu, int N);
 bool launch_wg(const KParams &p, hipStream_t stream, const char **name);
+// ... its prepared controller: one record per instance (wg_ctl_rec_layout), p.mode = MODE_CTL_FACTOR / MODE_CTL_STEP
+bool launch_wg_ctl(const KParams &p, hipStream_t stream, const char **name);
 
 // lqmpc_jit.hip: the 16-lane-row kernel (and the probe) of a shape without a prebuilt instantiation, compiled at run time
 bool jit_r16_shape(int nx, int nu, int N, int *lpi);

@@ -956,6 +956,103 @@ struct Wg {
         act_prev = (status == 2) ? 0.0 : act;
         return status;
     }
+
+    // ---------------- prepared controller (lqmpc_wg_ctl_*_kernel below): the set-up kept in one HBM record per instance ----------------
+    __device__ __forceinline__ void init_rows()
+    {
+        own = t < n;
+        R = Red{lds + o.red, 0};
+        h = own ? 0.5 * (p.sh[p.so.ub + t % nu] - p.sh[p.so.lb + t % nu]) : 1.0;
+        ctr = own ? 0.5 * (p.sh[p.so.ub + t % nu] + p.sh[p.so.lb + t % nu]) : 0.0;
+        vr = 0.0;
+        last_m = 0; act_prev = 0.0; v = 0.0; qs = 0.0; sl = su = zl = zu = 1.0; rd = 0.0;
+    }
+    __device__ __forceinline__ int image_count() const { return nb * (nb + 1) / 2 * BLK; }
+
+    // after setup(): everything a step needs, to the record.  A set-up that failed (a pivot of the factorisation, a non-finite G or v_r)
+    // is marked by NaN in v_r: every step of that instance then reports status 2.
+    __device__ __forceinline__ void store_record(double *rc, const WgCtlRec &L)
+    {
+        bool bad = false;
+        if (own) {
+            bad = !(fabs(vr) < 1e300);
+            for (int a = 0; a < nx; ++a) bad = bad || !(fabs(lds[o.G + a * np + t]) < 1e300);
+        }
+        bad = block_any(bad || *flag() == 0, R);
+        for (int e = t; e < nx * nx + nx * nu; e += THREADS) rc[L.oA + e] = lds[o.AB + e];
+        for (int e = t; e < np * nx; e += THREADS) rc[L.oG + e] = lds[o.G + e];
+        if (t < np) rc[L.oV + t] = bad ? __builtin_nan("") : (own ? vr : 0.0);
+        const int cnt = image_count();
+#pragma unroll
+        for (int m = 0; m < PREG; ++m) {
+            const int e = t + THREADS * m;
+            if (e < cnt) { rc[L.oW + e] = lds[o.K + e]; rc[L.oP + e] = preg[m]; }
+        }
+    }
+    // what every step reads: the shared block, the model, G and v_r
+    __device__ __forceinline__ void stage_record(const double *rc, const WgCtlRec &L)
+    {
+        ldsd *S = lds + o.SH;
+        for (int e = t; e < o.shn; e += THREADS) S[e] = p.sh[e];
+        for (int e = t; e < nx * nx + nx * nu; e += THREADS) lds[o.AB + e] = rc[L.oA + e];
+        for (int e = t; e < np * nx; e += THREADS) lds[o.G + e] = rc[L.oG + e];
+        vr = own ? rc[L.oV + t] : 0.0;
+    }
+    // what only the iterations read: W into the K region, P into the registers
+    __device__ __forceinline__ void load_W_P(const double *rc, const WgCtlRec &L)
+    {
+        const int cnt = image_count();
+#pragma unroll
+        for (int m = 0; m < PREG; ++m) {
+            const int e = t + THREADS * m;
+            double wv = 0.0, pv = 0.0;
+            if (e < cnt) { wv = rc[L.oW + e]; pv = rc[L.oP + e]; }
+            if (e < cnt) lds[o.K + e] = wv;
+            preg[m] = pv;
+        }
+        __syncthreads();
+    }
+    // u of every stage (clipped v plus the centre of the box) to LDS at vw
+    __device__ __forceinline__ void publish_u()
+    {
+        __syncthreads();
+        if (t < np) lds[o.vw + t] = own ? fmin(fmax(v, -h), h) + ctr : 0.0;
+        __syncthreads();
+    }
+    // V_N by rolling the model forward with the inputs at vw from the state at xs (as the solve kernel's value_fn); leaves the predicted
+    // states in Xs, A x + B u_0 at Xs[nx ..]
+    __device__ __forceinline__ double value_of()
+    {
+        ldsd *Xs = lds + o.Xs;
+        const ldsd *sh = shd();
+        const ldsd *A = lds + o.AB, *Bm = A + nx * nx, *uu = lds + o.vw;
+        if (t < nx) Xs[t] = lds[o.xs + t];
+        __syncthreads();
+        for (int s = 0; s < N; ++s) {
+            if (t < nx) Xs[(s + 1) * nx + t] = ldot(Bm + t * nu, 1, uu + s * nu, 1, nu, ldot(A + t * nx, 1, Xs + s * nx, 1, nx));
+            __syncthreads();
+        }
+        double c = 0.0;
+        if (t <= N) {
+            const int st = t;
+            const ldsd *Qs = sh + ((st == N) ? p.so.P : p.so.Q);
+            const bool rf = p.has_ref && st >= 1;
+            for (int i = 0; i < nx; ++i) {
+                const double di = Xs[st * nx + i] - (rf ? sh[p.so.xref + i * N + st - 1] : 0.0);
+                double r = 0.0;
+                for (int j = 0; j < nx; ++j) r = __builtin_fma(Qs[i * nx + j], Xs[st * nx + j] - (rf ? sh[p.so.xref + j * N + st - 1] : 0.0), r);
+                c = __builtin_fma(di, r, c);
+            }
+            if (st < N)
+                for (int k = 0; k < nu; ++k) {
+                    const double dk = uu[st * nu + k] - (p.has_ref ? sh[p.so.uref + k * N + st] : 0.0);
+                    double r = 0.0;
+                    for (int j = 0; j < nu; ++j) r = __builtin_fma(sh[p.so.R + k * nu + j], uu[st * nu + j] - (p.has_ref ? sh[p.so.uref + j * N + st] : 0.0), r);
+                    c = __builtin_fma(dk, r, c);
+                }
+        }
+        return block_sum(c, R);
+    }
 };
 
 __global__ void __launch_bounds__(256, 1) lqmpc_wg_kernel(KParams p)
@@ -1185,6 +1282,107 @@ __global__ void __launch_bounds__(256, 1) lqmpc_wg_kernel(KParams p)
         if (p.status) p.status[b] = status;
         if (p.iters) p.iters[b] = iters;
     }
+}
+
+// ---- prepared controller on this kernel's shapes: the set-up once (factor), then one QP per instance and call from its record (step) ----
+// Of a one-shot solve on these shapes the set-up is nearly everything, and nothing of it depends on the state.
+// Both kernels are built from the members of Wg; lqmpc_wg_kernel itself is not touched.  (They stand behind it: in front of it the
+// compiler folds one LDS address of lqmpc_wg_kernel differently.)
+__global__ void __launch_bounds__(256, 1) lqmpc_wg_ctl_factor_kernel(KParams p)
+{
+    extern __shared__ double lds_raw[];
+    ldsd *lds = (ldsd *)lds_raw;
+    const long long b = blockIdx.x;
+    const int nx = p.nx, nu = p.nu, N = p.N, n = p.n;
+    Wg w{p, wg_offsets(nx, nu, N), lds, n, (n + BS - 1) / BS, ((n + BS - 1) / BS) * BS, nx, nu, N, (int)threadIdx.x};
+    w.init_rows();
+    w.setup(b);
+    w.store_record(p.ctl_rec + b * p.ctl_stride, wg_ctl_rec_layout(nx, nu, N));
+}
+
+// Per instance in p.ctl_face, (4 + 2 nx) words: the face the previous step ended on (WG_CTL_FACE_WORDS row masks), the state it was
+// found at, the state A x + B u_0 the model expected next.  The rule is the 16-lane-row controller's: a state at least as near to the
+// expected one as to the previous one has advanced by a stage, and the face is shifted as the rollout shifts it; a state nearer to the
+// previous one (the same state asked again) keeps the face as it is.  All-zero masks: no face (first step, lqmpc_controller_reset).
+__global__ void __launch_bounds__(256, 1) lqmpc_wg_ctl_step_kernel(KParams p)
+{
+    extern __shared__ double lds_raw[];
+    ldsd *lds = (ldsd *)lds_raw;
+    const int t = threadIdx.x;
+    const long long b = blockIdx.x, Bsz = p.Bsz;
+    const int nx = p.nx, nu = p.nu, N = p.N, n = p.n;
+    Wg w{p, wg_offsets(nx, nu, N), lds, n, (n + BS - 1) / BS, ((n + BS - 1) / BS) * BS, nx, nu, N, t};
+    w.init_rows();
+    const WgCtlRec L = wg_ctl_rec_layout(nx, nu, N);
+    const double *rc = p.ctl_rec + b * p.ctl_stride;
+    unsigned long long *fc = p.ctl_face + b * (WG_CTL_FACE_WORDS + 2 * nx);
+    ldsd *xs = lds + w.o.xs;
+    w.stage_record(rc, L);
+    if (t < nx) xs[t] = p.x0[(long long)t * Bsz + b];
+    __syncthreads();
+    const double vu = w.vunc();
+    const int chk = block_any3(w.own && !(fabs(vu) <= w.h), w.own && !(fabs(vu) < 1e300), false, w.R);
+    int iters = 0, status = 0;
+    bool keep_face = false;
+    if (!(chk & 1)) {
+        w.v = vu;                                                 // the unconstrained minimiser is inside the box: W is never read
+    } else if (chk & 2) {
+        w.v = 0.0; status = 2; keep_face = true;                  // a non-finite state (or a failed set-up): the stored face stays
+    } else {
+        w.load_W_P(rc, L);
+        // the stored face, and whether the state has advanced since it was found
+        const int wv = t >> 6;
+        const unsigned long long lo = wv < 2 ? fc[2 * wv] : 0ull, up = wv < 2 ? fc[2 * wv + 1] : 0ull;
+        w.act_prev = !w.own ? 0.0 : (((lo >> (t & 63)) & 1ull) ? -1.0 : (((up >> (t & 63)) & 1ull) ? 1.0 : 0.0));
+        double dprev = 0.0, dnext = 0.0;
+        for (int a = 0; a < nx; ++a) {
+            const double e0 = xs[a] - __longlong_as_double((long long)fc[WG_CTL_FACE_WORDS + a]);
+            const double e1 = xs[a] - __longlong_as_double((long long)fc[WG_CTL_FACE_WORDS + nx + a]);
+            dprev = __builtin_fma(e0, e0, dprev);
+            dnext = __builtin_fma(e1, e1, dnext);
+        }
+        // solve_qp hands the iterations the face moved up by Wg::nu rows (one stage); a distance of n rows leaves every row where it is
+        w.nu = __builtin_amdgcn_readfirstlane(dprev < dnext ? n : nu);
+        status = w.solve_qp(iters);
+        w.nu = nu;
+    }
+    w.publish_u();
+    const ldsd *uu = lds + w.o.vw;
+    if (t < nu) p.u0[(long long)t * Bsz + b] = uu[t];
+    if (p.VN) {
+        const double vn = w.value_of();
+        if (t == 0) p.VN[b] = vn;
+    }
+    if (!keep_face) {
+        const unsigned long long lo = __ballot(w.own && w.act_prev < 0.0), up = __ballot(w.own && w.act_prev > 0.0);
+        if ((t & 63) == 0 && t < 128) { fc[2 * (t >> 6)] = lo; fc[2 * (t >> 6) + 1] = up; }
+        if (t < nx) {
+            const ldsd *A = lds + w.o.AB, *Bm = A + nx * nx;
+            const double xn = ldot(Bm + t * nu, 1, uu, 1, nu, ldot(A + t * nx, 1, xs, 1, nx));
+            fc[WG_CTL_FACE_WORDS + t] = (unsigned long long)__double_as_longlong(xs[t]);
+            fc[WG_CTL_FACE_WORDS + nx + t] = (unsigned long long)__double_as_longlong(xn);
+        }
+    }
+    if (t == 0) {
+        if (p.status) p.status[b] = status;
+        if (p.iters) p.iters[b] = iters;
+    }
+}
+
+// p.mode: MODE_CTL_FACTOR or MODE_CTL_STEP
+bool launch_wg_ctl(const KParams &p, hipStream_t stream, const char **name)
+{
+    if (p.mode != MODE_CTL_FACTOR && p.mode != MODE_CTL_STEP) return false;
+    const size_t bytes = wg_lds_bytes(p.nx, p.nu, p.N);
+    void (*kern)(KParams) = p.mode == MODE_CTL_FACTOR ? lqmpc_wg_ctl_factor_kernel : lqmpc_wg_ctl_step_kernel;
+    const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) {
+        fprintf(stderr, "lqmpc: hipFuncSetAttribute(%zu bytes of LDS): %s\n", bytes, hipGetErrorString(e));
+        return false;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.Bsz), dim3(256), bytes, stream, p);
+    if (name) *name = p.mode == MODE_CTL_FACTOR ? "lqmpc_wg_ctl_factor_kernel" : "lqmpc_wg_ctl_step_kernel";
+    return true;
 }
 
 bool launch_wg(const KParams &p, hipStream_t stream, const char **name)

@@ -293,7 +293,12 @@ class BatchController:
     (a simulator in torch, recorded data, hardware): the states come from outside, only u_0 comes from here.
 
     A, B: numpy arrays (nx, nx, Bsz) / (nx, nu, Bsz) or device tensors of those shapes (anything with .shape and .data_ptr()).
-    The controller runs under the solver's options as they are NOW; it keeps the solver alive and must be closed before it."""
+    The controller runs under the solver's options as they are NOW; it keeps the solver alive and must be closed before it.
+
+    Where the solver runs the 16-lane-row kernels the controller keeps one record per instance.  On the workgroup kernel's shapes
+    (32 < N * nu <= 128, e.g. (8, 4, 30)) it does so only if the solver has ctl_wg=1 when the controller is made
+    (solver.set_options(ctl_wg=1): 166 KB per instance at (8, 4, 30)); otherwise, and on every other shape, each step is a full
+    solve_batch_dev.  `kernel` says which: a record controller's name contains "ctl"."""
 
     def __init__(self, solver, N, A, B, Q, R, P, lb, ub, x_ref=None, u_ref=None):
         self._c = None

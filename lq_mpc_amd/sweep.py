@@ -108,7 +108,7 @@ class LQ_RDP_Behavior_Multiple:
         s = self._s()
         while len(self._handles) < k:
             self._handles.append(BatchSolver(s.device))
-        opts = {key: v for key, v in s.get_options().items() if key not in ("struct_size", "reserved", "reserved2")}
+        opts = {key: v for key, v in s.get_options().items() if key not in ("struct_size", "reserved")}
         for hd in self._handles[:k]:
             hd.set_options(**opts)
         return self._handles[:k]

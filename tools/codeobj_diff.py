@@ -50,6 +50,11 @@ def kernels(obj):
             if cur and cur[-1].startswith("s_getpc_b64") and txt.startswith("s_add_u32"):
                 txt = txt.rsplit(",", 1)[0] + ", <pc-relative>"      # the distance to another function of the code object: moves with its neighbours
             cur.append(txt)
+    for lines in text.values():
+        # padding behind a function's last instruction (alignment of the next function; 256 s_nop behind the last function of the code
+        # object): never executed, and it moves when a function is added elsewhere in the file
+        while len(lines) > 1 and lines[-1] == "s_nop 0" and lines[-2].split()[0] in ("s_nop", "s_endpgm", "s_setpc_b64"):
+            lines.pop()
     res, name, vals = {}, None, {}
     for ln in subprocess.run([READELF, "--notes", obj], capture_output=True, text=True, check=True).stdout.splitlines():
         m = re.match(r"\s*-?\s*(\.[a-z_]+):\s*(\S+)", ln)

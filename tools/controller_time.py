@@ -1,6 +1,8 @@
 """Times a prepared controller's step against a one-shot solve at the headline shape; prints one JSON line.
 
-    python tools/controller_time.py [--config 3] [--calls 20] [--rounds 5]
+    python tools/controller_time.py [--config 3] [--calls 20] [--rounds 5] [--out FILE]
+    python tools/controller_time.py --config 5          (records on the workgroup kernel's shapes, options.ctl_wg = 1;
+                                                         also written to profiles/controller_c5.json)
 
 Per mix (default, hard): 20 lqmpc_solve_batch_dev calls and 20 BatchController.step_dev calls on the same states, measured
 alternately with the handle's own timer after three warm-up rounds, median of the rounds; the step both repeated (warm face)
@@ -22,11 +24,16 @@ def main():
     ap.add_argument("--config", type=int, default=3)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file (default for --config 5: profiles/controller_c5.json)")
     a = ap.parse_args()
+    if a.out is None and a.config == 5:
+        a.out = os.path.join(ROOT, "profiles", "controller_c5.json")
     import torch
     from lq_mpc_amd import BatchController, BatchSolver, synth
     torch.cuda.init()                                     # torch opens the GPU before the library does
     s = BatchSolver(0)
+    if a.config == 5:
+        s.set_options(ctl_wg=1)                           # the workgroup kernel's shapes keep records only on request
     out = {"tool": "controller_time", "config": a.config, "calls": a.calls, "rounds": a.rounds, "device": torch.cuda.get_device_name(0)}
     for mix in ("default", "hard"):
         b = synth.make_batch(a.config, mix=mix)
@@ -82,6 +89,9 @@ def main():
         ctl.close()
     s.close()
     print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
 
 
 if __name__ == "__main__":
