@@ -301,6 +301,12 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
  *   instance and leaves no trace in the controller.  A step sets the handle's lqmpc_last_kernel.
  * reset: forget the stored active sets (the next step starts cold).  bytes: HBM held by the controller.  kernel: the kernel its
  *   steps launch (contains "ctl"), or for a pass-through controller the kernel its last step ran.  destroy: NULL is fine.
+ * set_reference: new references for every later step, x_ref (nx x N) and u_ref (nu x N) HOST, row-major, NULL = zeros -- for a loop
+ *   that tracks a moving setpoint or slides its N-stage window along a trajectory.  Of a record only v_r depends on the references
+ *   (v_r = -2 W g_ref - centre of the box, g_ref from an N-step costate recursion on the record's A and B): one launch rewrites it in
+ *   place (lqmpc_ctl_retarget_kernel / lqmpc_wg_ctl_retarget_kernel), enqueued on the handle's stream, so it is ordered with the
+ *   steps.  The arrays are copied before the call returns, and it does not wait for the stream.  A pass-through controller only
+ *   stores them.  The stored active sets are kept (a warm-start hint that never decides the answer; reset forgets them).
  * lqmpc_jit_compile_controller: the two kernels (factor, step) of a shape without prebuilt ones, compiled (or found in the cache
  *   directory) now; needs no GPU; returns 2 or a negative lqmpc_error. */
 typedef struct lqmpc_controller lqmpc_controller;
@@ -317,6 +323,7 @@ int lqmpc_controller_create_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t 
 int lqmpc_controller_step(lqmpc_controller *c, const double *x, double *u0, double *VN, int32_t *status, int32_t *iters);
 int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, int32_t *dstatus, int32_t *diters);
 int lqmpc_controller_reset(lqmpc_controller *c);
+int lqmpc_controller_set_reference(lqmpc_controller *c, const double *x_ref, const double *u_ref);
 int64_t lqmpc_controller_bytes(const lqmpc_controller *c);
 const char *lqmpc_controller_kernel(const lqmpc_controller *c);
 int lqmpc_controller_destroy(lqmpc_controller *c);

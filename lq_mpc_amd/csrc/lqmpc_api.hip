@@ -1358,6 +1358,30 @@ int lqmpc_controller_reset(lqmpc_controller *c)
     return 0;
 }
 
+int lqmpc_controller_set_reference(lqmpc_controller *c, const double *x_ref, const double *u_ref)
+{
+    if (!c) return fail(LQMPC_ERR_BAD_ARG, "controller is NULL");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    // the controller's own copies: every later step packs the shared block from them, and the caller's arrays are free at once
+    c->has_xref = x_ref != nullptr;
+    c->has_uref = u_ref != nullptr;
+    if (x_ref) c->xref.assign(x_ref, x_ref + c->nx * c->N); else c->xref.clear();
+    if (u_ref) c->uref.assign(u_ref, u_ref + c->nu * c->N); else c->uref.clear();
+    if (!c->fast) return 0;
+    // records: v_r is the one entry that depends on the references.  The shared block goes up as for a step (pinned staging, ordered
+    // on the stream), then one launch rewrites v_r in place -- behind every step enqueued so far, in front of every later one.
+    KParams p;
+    Plan pl;
+    int rc = prepare(h, c->opt, ctl_call(c), p, pl);
+    if (rc) return rc;
+    ctl_bind(c, p);
+    if (!(c->wg ? lqmpc::launch_wg_ctl_retarget(p, h->stream) : lqmpc::launch_ctl_retarget(p, h->stream)))
+        return fail(LQMPC_ERR_HIP, "controller retarget kernel launch failed");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int64_t lqmpc_controller_bytes(const lqmpc_controller *c) { return c ? (int64_t)c->bytes : 0; }
 
 const char *lqmpc_controller_kernel(const lqmpc_controller *c) { return c ? c->name.c_str() : "none"; }

@@ -49,4 +49,9 @@ bool launch_jit_bounds(int device, const BoundsParams &p, hipStream_t stream, st
 bool ctl_available(int nx, int nu, int N);
 bool launch_ctl(const KParams &p, hipStream_t stream, const char **name);
 
+// lqmpc_ctl_ref.hip: new references for a prepared controller -- v_r of every record rewritten in place from the shared block
+// (p.sh, p.has_ref) and the record's own A, B, W; run-time dimensions, so the run-time compiled shapes are served as well
+bool launch_ctl_retarget(const KParams &p, hipStream_t stream);          // ctl_rec_layout records
+bool launch_wg_ctl_retarget(const KParams &p, hipStream_t stream);       // wg_ctl_rec_layout records
+
 }  // namespace lqmpc

@@ -347,6 +347,14 @@ class BatchController:
         """Forget the active sets carried from the previous step: the next step starts cold."""
         _lib.check(self._L.lqmpc_controller_reset(self._live()))
 
+    def set_reference(self, x_ref=None, u_ref=None):
+        """New references (nx, N) / (nu, N) for every later step; None means zeros.  On a record controller one launch rewrites
+        the part of the records that depends on them, enqueued on the solver's stream like a step; the arrays are copied before
+        this returns.  The carried active sets are kept: they only warm-start the next step (reset() forgets them)."""
+        c = self._live()
+        x_ref, u_ref = _ref_or_none(x_ref, self.nx, self.N), _ref_or_none(u_ref, self.nu, self.N)
+        _lib.check(self._L.lqmpc_controller_set_reference(c, _ptr(x_ref), _ptr(u_ref)))
+
     @property
     def kernel(self):
         return self._L.lqmpc_controller_kernel(self._live()).decode()

@@ -6,7 +6,12 @@
 
 Per mix (default, hard): 20 lqmpc_solve_batch_dev calls and 20 BatchController.step_dev calls on the same states, measured
 alternately with the handle's own timer after three warm-up rounds, median of the rounds; the step both repeated (warm face)
-and after reset() (cold; the figure includes the reset's fill of the stored faces)."""
+and after reset() (cold; the figure includes the reset's fill of the stored faces).
+
+    python tools/controller_time.py --retarget [--config 3|5]
+New references in every call (two sets taken in turn, default mix): set_reference alone, set_reference + step with the face kept,
+set_reference + reset + step, destroy + create + step, and the one-shot solve with the same references; the result is kept under
+"C<config>" in profiles/controller_retarget.json."""
 import argparse
 import json
 import os
@@ -25,8 +30,9 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file (default for --config 5: profiles/controller_c5.json)")
+    ap.add_argument("--retarget", action="store_true", help="time set_reference against re-creating the controller and against a one-shot solve")
     a = ap.parse_args()
-    if a.out is None and a.config == 5:
+    if a.out is None and a.config == 5 and not a.retarget:
         a.out = os.path.join(ROOT, "profiles", "controller_c5.json")
     import torch
     from lq_mpc_amd import BatchController, BatchSolver, synth
@@ -35,6 +41,9 @@ def main():
     if a.config == 5:
         s.set_options(ctl_wg=1)                           # the workgroup kernel's shapes keep records only on request
     out = {"tool": "controller_time", "config": a.config, "calls": a.calls, "rounds": a.rounds, "device": torch.cuda.get_device_name(0)}
+    if a.retarget:
+        retarget(a, s, out, torch)
+        return
     for mix in ("default", "hard"):
         b = synth.make_batch(a.config, mix=mix)
         nx, nu, Bsz = b["B"].shape
@@ -92,6 +101,61 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
+
+
+def retarget(a, s, out, torch):
+    from lq_mpc_amd import BatchController, synth
+    b = synth.make_batch(a.config)
+    nx, nu, Bsz = b["B"].shape
+    N = b["N"]
+    rng = np.random.default_rng(5)
+    R = [(0.1 * rng.standard_normal((nx, N)), 0.05 * rng.standard_normal((nu, N))) for _ in range(2)]
+    dev = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()
+    dA, dB, dx = dev(b["A"]), dev(b["B"]), dev(b["x0"])
+    du = torch.empty((nu, Bsz), dtype=torch.float64, device="cuda")
+    dv = torch.empty(Bsz, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    s.reserve(nx, nu, N, Bsz)
+    fixed = (b["Q"], b["R"], b["P"], b["lb"], b["ub"])
+    ctl = [BatchController(s, N, dA, dB, *fixed)]
+
+    def timed(body):
+        s.timer_begin()
+        for k in range(a.calls):
+            body(k)
+        return s.timer_end() / a.calls
+
+    def set_step(k, cold):
+        ctl[0].set_reference(*R[k & 1])
+        if cold:
+            ctl[0].reset()
+        ctl[0].step_dev(dx, du, dv)
+
+    def recreate(k):
+        ctl[0].close()
+        ctl[0] = BatchController(s, N, dA, dB, *fixed, *R[k & 1])
+        ctl[0].step_dev(dx, du, dv)
+
+    legs = {"t_set_reference_ms": lambda k: ctl[0].set_reference(*R[k & 1]),
+            "t_set_reference_step_warm_ms": lambda k: set_step(k, False),
+            "t_set_reference_step_cold_ms": lambda k: set_step(k, True),
+            "t_destroy_create_step_ms": recreate,
+            "t_solve_with_references_ms": lambda k: s.solve_batch_dev(nx, nu, N, Bsz, dA, dB, *fixed, dx, du, dv, x_ref=R[k & 1][0], u_ref=R[k & 1][1])}
+    for _ in range(3):
+        for f in legs.values():
+            timed(f)
+    r = [{k: timed(f) for k, f in legs.items()} for _ in range(a.rounds)]
+    res = {k: round(float(np.median([q[k] for q in r])), 5) for k in legs}
+    rec = ctl[0].nbytes / Bsz
+    res.update(shape=[nx, nu, N], Bsz=Bsz, kernel=ctl[0].kernel, bytes_per_instance=rec, device=out["device"], calls=a.calls, rounds=a.rounds)
+    ctl[0].close()
+    s.close()
+    path = a.out or os.path.join(ROOT, "profiles", "controller_retarget.json")
+    allr = json.load(open(path)) if os.path.exists(path) else {"tool": "controller_time --retarget"}
+    allr[f"C{a.config}"] = res
+    print(json.dumps({f"C{a.config}": res}))
+    with open(path, "w") as f:
+        f.write(json.dumps(allr, indent=1) + "\n")
 
 
 if __name__ == "__main__":
