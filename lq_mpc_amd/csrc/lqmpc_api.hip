@@ -64,7 +64,7 @@ struct lqmpc_handle {
 
 constexpr int JIT_FALLBACK_COLS = 1024;   // workspace columns of the generic kernel when it only serves a hand-back list
 
-constexpr size_t HIST_INTS = (size_t)lqmpc::ORDER_CELLS * lqmpc::ORDER_PAD;
+constexpr size_t HIST_INTS = (size_t)lqmpc::ORDER_BUCKETS * lqmpc::ORDER_PAD;
 constexpr size_t FAIL_HDR = 16 + 2 * HIST_INTS;    // ints in front of the hand-back list: its count, the order's two alternating sets of counters
 
 static int ensure_host(HostBuf &b, size_t bytes)
@@ -426,6 +426,8 @@ static int make_plan(const lqmpc_options &o, const Call &c, int device, Plan &pl
     // The difficulty order of a rollout (options.order; the two-launch sweep leaves it to the rollout it calls).  The packed family
     // orders from 1 024 instances; the 16-lane-row family from 8 192 (measured at C3: the sorted walk pays for its probe and scatter
     // launches from about 8 192 instances: 0.26 against 0.31 ms at 16 384, 0.25 against 0.19 ms at 4 096).
+    // Measured again with the cheaper probe and scatter (C3, T = 30, order on against off): 0.176 against 0.150 ms at 4 096, 0.191 against
+    // 0.179 ms at 8 192, 0.195 against 0.215 ms at 16 384.  The crossing still lies between 8 192 and 16 384; the threshold stays.
     const bool rollout = c.mode == lqmpc::MODE_ROLLOUT || c.mode == lqmpc::MODE_SWEEP;
     const bool packed_size = c.T >= 4 && c.Bsz >= 1024;
     if (pl.rows()) pl.order = rollout && (o.order < 0 ? (c.T >= 4 && c.Bsz >= 8192) : o.order == 1);

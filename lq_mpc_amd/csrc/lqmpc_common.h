@@ -49,7 +49,7 @@ struct KParams {
     int *status, *iters;                  // may be null
     const int *perm;                      // processing order (slot -> instance), null = natural order
     double *key;                          // MODE_PROBE output per instance: (difficulty bucket, position inside the bucket), two ints
-    int *hist;                            // MODE_PROBE: instances per difficulty bucket (ORDER_CELLS counters, zero on entry)
+    int *hist;                            // MODE_PROBE: instances per difficulty bucket (ORDER_BUCKETS counters, ORDER_PAD ints apart, zero on entry)
     int *hist_next;                       // MODE_PROBE: the counters of the NEXT call, zeroed by this launch (the two sets alternate: no fill launch per call)
     double *stage;                        // MODE_PROBE output: instance-major [A|B|x0] records (null: none)
     const double *rec;                    // input records staged by the probe (null: read A, B, x0 directly)
@@ -98,9 +98,9 @@ __host__ __device__ constexpr WgCtlRec wg_ctl_rec_layout(int nx, int nu, int N)
 constexpr int WG_CTL_FACE_WORDS = 4;         // per instance in front of the two states: (lower, upper) row masks of rows 0..63, then of rows 64..127
 
 constexpr int ORDER_BUCKETS = 512;          // difficulty buckets of the ordering: 16 per binade of the key over [2^-2, 2^30)
-constexpr int ORDER_COPIES = 8;              // counters per bucket (wavefront w uses copy w % 8): spreads the atomics on a popular bucket
-constexpr int ORDER_CELLS = ORDER_BUCKETS * ORDER_COPIES;
 constexpr int ORDER_PAD = 16;                // ints between two counters: one 64-byte line each (atomics on one line serialise)
+constexpr int PROBE_WG = 256;                // instances (lanes) per workgroup of the probe: it reserves a bucket's positions once per workgroup
+constexpr int SCATTER_PER_WG = 512;          // instances a workgroup of lqmpc_order_scatter_kernel places
 
 // ---- fp64 reciprocal / reciprocal square root: hardware seed + Newton steps ----
 // v_rcp_f64 / v_rsq_f64 give a seed good to ~2^-26 or better; two Newton steps reach ~1 ulp

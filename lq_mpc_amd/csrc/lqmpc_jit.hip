@@ -120,7 +120,7 @@ static std::string program_text(int nx, int nu, int N, int mode)
     }
     if (mode == MODE_PROBE) {
         snprintf(buf, sizeof buf,
-                 "#include \"lqmpc_probe.h\"\nnamespace lqmpc {\nextern \"C\" __global__ void __launch_bounds__(64) lqmpc_jit_kernel(KParams p)\n"
+                 "#include \"lqmpc_probe.h\"\nnamespace lqmpc {\nextern \"C\" __global__ void __launch_bounds__(PROBE_WG) lqmpc_jit_kernel(KParams p)\n"
                  "{ probe_body<%d, %d, %d>(p); }\n}\n", nx, nu, N);
         return buf;
     }
@@ -256,15 +256,15 @@ bool launch_jit(int device, const KParams &p, hipStream_t stream, const char **n
     std::string err;
     const Loaded *l = get_kernel(device, p.nx, p.nu, p.N, p.mode, err);
     if (!l) { if (why) *why = err; return false; }
-    unsigned grid;
-    if (p.mode == MODE_PROBE) grid = (unsigned)((p.Bsz + 63) / 64);
+    unsigned grid, block = 64;
+    if (p.mode == MODE_PROBE) { grid = (unsigned)((p.Bsz + PROBE_WG - 1) / PROBE_WG); block = PROBE_WG; }
     else {
         const int ipw = 64 / jit_lanes(p.nx, p.nu, p.N);
         grid = (unsigned)((p.Bsz + ipw - 1) / ipw);
     }
     KParams arg = p;
     void *args[] = {&arg};
-    const hipError_t e = hipModuleLaunchKernel(l->fn, grid, 1, 1, 64, 1, 1, 0, stream, args, nullptr);
+    const hipError_t e = hipModuleLaunchKernel(l->fn, grid, 1, 1, block, 1, 1, 0, stream, args, nullptr);
     if (e != hipSuccess) { if (why) *why = std::string("hipModuleLaunchKernel: ") + hipGetErrorString(e); return false; }
     if (name) {
         std::lock_guard<std::mutex> lock(g_mu);

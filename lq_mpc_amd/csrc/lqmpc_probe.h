@@ -8,28 +8,49 @@
 namespace lqmpc {
 
 // ---------------- difficulty probe (options.order) ----------------
-// One instance per lane.  Two keys: for rollouts on a shared plant a clipped roll of that plant (order_roll, below); otherwise the
-// largest stage gradient of the FREE response over the horizon, in
+// One instance per lane, PROBE_WG instances per workgroup.  Two keys: for rollouts on a shared plant a clipped roll of that plant
+// (order_roll, below); otherwise the largest stage gradient of the FREE response over the horizon, in
 // units of what one input can counter:  max_r max_k |B_k' Q A^(r+1) x0| / ((B'QB + R)_kk h_k).
 // It needs neither condensing nor a factorisation (240 FMAs per instance at C3) and orders the batch
 // almost as well as the exact overshoot of the unconstrained minimiser (20.5 % vs 19.8 % of wave-steps
 // left with a constrained instance on C3; natural order 48.7 %).  A heuristic: it only decides which
 // instances share a wavefront, never a result.  The same pass stages the instance-major [A | B | x0]
 // records the sorted walk reads.
+//
+// The records of a workgroup's instances are one contiguous piece of p.stage.  Where it fits in LDS (PROBE_WG records: C3's 56 KB)
+// the workgroup lays the piece out there and copies it out 16 bytes a lane, whole 64-byte lines a wavefront -- a lane storing its own
+// record field by field touches 64 lines with every store instruction (1.8 M eight-byte requests at C3 x 65 536).  Larger records
+// are stored by their lanes as before.
+//
+// Positions inside a bucket: the workgroup counts its instances per bucket in LDS (the LDS atomic hands every lane its rank), then
+// reserves each non-empty bucket's run with ONE global atomic, all of them in flight at once.
+template <int NX, int NU>
+struct ProbeRec {
+    static constexpr int REC = NX * NX + NX * NU + NX;
+    static constexpr bool DENSE = PROBE_WG * REC * 8 <= 56 * 1024;      // (+ 2 KB of counters: inside the 64 KB of a static allocation)
+};
+
 template <int NX, int NU, int N>
 __device__ __forceinline__ void probe_body(const KParams &p)
 {
+    constexpr int REC = ProbeRec<NX, NU>::REC;
+    constexpr bool DENSE = ProbeRec<NX, NU>::DENSE;
+    __shared__ int cnt[ORDER_BUCKETS];          // instances of this workgroup per bucket, then the start of their run in the bucket
+    __shared__ __attribute__((aligned(16))) double tr[DENSE ? PROBE_WG * REC : 2];
     const long long Bsz = p.Bsz;
-    const long long b = (long long)blockIdx.x * 64 + threadIdx.x;
+    const int tid = threadIdx.x;
+    const long long b0 = (long long)blockIdx.x * PROBE_WG, bt = b0 + tid;
+    const bool live = bt < Bsz;
+    const long long b = live ? bt : Bsz - 1;            // surplus lanes of the last workgroup shadow the last instance and write nothing
     // housekeeping that used to be a fill launch per call: the counters the NEXT call's probe will count into (the two sets
     // alternate; the last reader of that set, the previous call's scatter, is long done) and this call's hand-back count
     if (p.hist_next) {
-        const long long total = (long long)gridDim.x * 64;
-        for (long long e = b; e < (long long)ORDER_CELLS * ORDER_PAD; e += total) p.hist_next[e] = 0;
+        const long long total = (long long)gridDim.x * PROBE_WG;
+        for (long long e = bt; e < (long long)ORDER_BUCKETS * ORDER_PAD; e += total) p.hist_next[e] = 0;
     }
-    if (p.fail_count && b == 0) { p.fail_count[0] = 0; p.fail_count[1] = 0; }
-    if (b >= Bsz) return;
-    constexpr int REC = NX * NX + NX * NU + NX;
+    if (p.fail_count && bt == 0) { p.fail_count[0] = 0; p.fail_count[1] = 0; }
+#pragma unroll
+    for (int k = 0; k < ORDER_BUCKETS / PROBE_WG; ++k) cnt[tid + k * PROBE_WG] = 0;
     const double *sh = p.sh;
     double A[NX][NX], Bm[NX][NU], x[NX];
 #pragma unroll
@@ -40,7 +61,18 @@ __device__ __forceinline__ void probe_body(const KParams &p)
         for (int k = 0; k < NU; ++k) Bm[i][k] = p.B[(long long)(i * NU + k) * Bsz + b];
         x[i] = p.x0[(long long)i * Bsz + b];
     }
-    if (p.stage) {
+    if constexpr (DENSE) {
+        if (p.stage) {
+#pragma unroll
+            for (int i = 0; i < NX; ++i) {
+#pragma unroll
+                for (int j = 0; j < NX; ++j) tr[tid * REC + i * NX + j] = A[i][j];
+#pragma unroll
+                for (int k = 0; k < NU; ++k) tr[tid * REC + NX * NX + i * NU + k] = Bm[i][k];
+                tr[tid * REC + NX * NX + NX * NU + i] = x[i];
+            }
+        }
+    } else if (p.stage && live) {
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
 #pragma unroll
@@ -48,6 +80,21 @@ __device__ __forceinline__ void probe_body(const KParams &p)
 #pragma unroll
             for (int k = 0; k < NU; ++k) p.stage[b * REC + NX * NX + i * NU + k] = Bm[i][k];
             p.stage[b * REC + NX * NX + NX * NU + i] = x[i];
+        }
+    }
+    __syncthreads();                                    // the counters are zero, the records lie in LDS
+    if constexpr (DENSE) {
+        if (p.stage) {
+            // the workgroup's piece: nrec records from b0 on, 16-byte aligned (PROBE_WG * REC doubles a workgroup), copied in pairs
+            const long long left = Bsz - b0;
+            const int nd = (int)(left < PROBE_WG ? left : PROBE_WG) * REC;
+            double *dst = p.stage + b0 * REC;
+#pragma unroll
+            for (int k = 0; k < (REC + 1) / 2; ++k) {
+                const int e = 2 * (tid + k * PROBE_WG);
+                if (e + 1 < nd) *(double2 *)(dst + e) = *(const double2 *)(tr + e);
+                else if (e < nd) dst[e] = tr[e];
+            }
         }
     }
     int raw;
@@ -153,34 +200,23 @@ __device__ __forceinline__ void probe_body(const KParams &p)
         const double kk = (key == key) ? key : 1e300;
         // The order only has to group similar instances, hardest first: a bucket sort on the logarithm of the key (exponent and
         // four mantissa bits of the fp64: 16 buckets per binade, clamped to [2^-2, 2^30): an instance whose key is below 1/4 never meets its bounds; finer buckets cost more atomics
-        // than they save in the rollout.  Each wavefront reserves its
-        // positions inside a bucket with one atomic per distinct bucket it holds; lqmpc_order_scatter_kernel turns
-        // (bucket, position) into the slot of the instance.
+        // than they save in the rollout.  lqmpc_order_scatter_kernel turns (bucket, position) into the slot of the instance.
         raw = (int)((unsigned)__double2hiint(kk) >> 16) - ((1023 - 2) << 4);
     }
     const int bucket = raw < 0 ? 0 : (raw > ORDER_BUCKETS - 1 ? ORDER_BUCKETS - 1 : raw);
-    const int lane = threadIdx.x;
-    int my_leader = lane, rank = 0, cnt = 0;           // the lanes of my bucket: first of them, my rank among them, their number
-    unsigned long long todo = __ballot(1);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int lb = __shfl(bucket, leader);
-        const unsigned long long same = __ballot(bucket == lb);
-        if (bucket == lb) {
-            my_leader = leader;
-            rank = __popcll(same & ((1ull << lane) - 1ull));
-            cnt = __popcll(same);
-        }
-        todo &= ~same;
+    const int rank = live ? atomicAdd(&cnt[bucket], 1) : 0;          // (LDS) my position among the workgroup's instances of my bucket
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < ORDER_BUCKETS / PROBE_WG; ++k) {
+        const int e = tid + k * PROBE_WG;
+        const int c = cnt[e];
+        if (c) cnt[e] = atomicAdd(&p.hist[e * ORDER_PAD], c);           // all the workgroup's reservations in flight at once
     }
-    const int cell = bucket * ORDER_COPIES + (int)(blockIdx.x % ORDER_COPIES);
-    int base = 0;
-    if (lane == my_leader) base = atomicAdd(&p.hist[cell * ORDER_PAD], cnt);   // all the wave's reservations in flight at once
-    base = __shfl(base, my_leader);
-    ((int2 *)p.key)[b] = make_int2(cell, base + rank);
+    __syncthreads();
+    if (live) ((int2 *)p.key)[b] = make_int2(bucket, cnt[bucket] + rank);
 }
 
 template <int NX, int NU, int N>
-__global__ void __launch_bounds__(64) lqmpc_probe_kernel(KParams p) { probe_body<NX, NU, N>(p); }
+__global__ void __launch_bounds__(PROBE_WG) lqmpc_probe_kernel(KParams p) { probe_body<NX, NU, N>(p); }
 
 }  // namespace lqmpc

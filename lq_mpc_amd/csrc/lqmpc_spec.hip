@@ -1170,38 +1170,45 @@ __global__ void __launch_bounds__(64, 1) lqmpc_spec_tiered_kernel(KParams p)
 }
 
 // slot of an instance = instances in harder buckets + its position inside its bucket.  Every block scans the bucket counts
-// itself (4096 counters: cheaper than another launch) and places 1024 instances.
+// itself (512 counters, two a thread, one barrier: cheaper than another launch) and places SCATTER_PER_WG instances.
 __global__ void __launch_bounds__(256) lqmpc_order_scatter_kernel(const int2 *where, const int *hist, int *perm, long long Bsz)
 {
-    __shared__ int base[ORDER_CELLS];
-    __shared__ int part[256];
-    constexpr int PER = ORDER_CELLS / 256;
-    const int t = threadIdx.x;
-    int above_in_chunk[PER], sum = 0;
+    static_assert(ORDER_BUCKETS == 2 * 256 && SCATTER_PER_WG % 256 == 0, "two counters a thread");
+    __shared__ int base[ORDER_BUCKETS];
+    __shared__ int wtot[4];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const long long i0 = (long long)blockIdx.x * SCATTER_PER_WG;
+    int2 wh[SCATTER_PER_WG / 256];
 #pragma unroll
-    for (int e = PER - 1; e >= 0; --e) { above_in_chunk[e] = sum; sum += hist[(PER * t + e) * ORDER_PAD]; }
-    part[t] = sum;
-    __syncthreads();
-    for (int d = 1; d < 256; d *= 2) {                       // inclusive suffix sums over the threads' chunks
-        const int v = part[t] + (t + d < 256 ? part[t + d] : 0);
-        __syncthreads();
-        part[t] = v;
-        __syncthreads();
+    for (int k = 0; k < SCATTER_PER_WG / 256; ++k) {          // (in flight with the counters)
+        const long long i = i0 + k * 256 + t;
+        wh[k] = i < Bsz ? where[i] : make_int2(0, 0);
     }
-    const int above = part[t] - sum;
+    const int c0 = hist[(2 * t) * ORDER_PAD], c1 = hist[(2 * t + 1) * ORDER_PAD];
+    int s = c0 + c1;                                         // inclusive suffix sums over the wavefront's pairs, then over the wavefronts
 #pragma unroll
-    for (int e = 0; e < PER; ++e) base[PER * t + e] = above + above_in_chunk[e];
+    for (int d = 1; d < 64; d *= 2) {
+        const int v = __shfl_down(s, d);
+        s += lane + d < 64 ? v : 0;
+    }
+    if (lane == 0) wtot[w] = s;
     __syncthreads();
-    const long long i0 = (long long)blockIdx.x * 1024;
-    for (long long i = i0 + t; i < i0 + 1024 && i < Bsz; i += 256) {
-        const int2 w = where[i];
-        perm[base[w.x] + w.y] = (int)i;
+    int above = s - (c0 + c1);
+#pragma unroll
+    for (int ww = 1; ww < 4; ++ww) above += ww > w ? wtot[ww] : 0;
+    base[2 * t + 1] = above;
+    base[2 * t] = above + c1;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SCATTER_PER_WG / 256; ++k) {
+        const long long i = i0 + k * 256 + t;
+        if (i < Bsz) perm[base[wh[k].x] + wh[k].y] = (int)i;
     }
 }
 
 void launch_order_scatter(const KParams &p, int *perm, hipStream_t stream)
 {
-    hipLaunchKernelGGL(lqmpc_order_scatter_kernel, dim3((unsigned)((p.Bsz + 1023) / 1024)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(lqmpc_order_scatter_kernel, dim3((unsigned)((p.Bsz + SCATTER_PER_WG - 1) / SCATTER_PER_WG)), dim3(256), 0, stream,
                        (const int2 *)p.key, (const int *)p.hist, perm, (long long)p.Bsz);
 }
 
@@ -1236,7 +1243,7 @@ static void launch_one(const KParams &p, hipStream_t stream)
     else if (p.mode == MODE_MAXVN)
         hipLaunchKernelGGL((lqmpc_spec_kernel<NX, NU, N, LPS, MODE_MAXVN>), dim3(grid), dim3(64), 0, stream, p);
     else if (p.mode == MODE_PROBE)
-        hipLaunchKernelGGL((lqmpc_probe_kernel<NX, NU, N>), dim3((unsigned)((p.Bsz + 63) / 64)), dim3(64), 0, stream, p);
+        hipLaunchKernelGGL((lqmpc_probe_kernel<NX, NU, N>), dim3((unsigned)((p.Bsz + PROBE_WG - 1) / PROBE_WG)), dim3(PROBE_WG), 0, stream, p);
     else
         hipLaunchKernelGGL((lqmpc_spec_kernel<NX, NU, N, LPS, MODE_ROLLOUT>), dim3(grid), dim3(64), 0, stream, p);
 }
