@@ -307,6 +307,19 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
  *   place (lqmpc_ctl_retarget_kernel / lqmpc_wg_ctl_retarget_kernel), enqueued on the handle's stream, so it is ordered with the
  *   steps.  The arrays are copied before the call returns, and it does not wait for the stream.  A pass-through controller only
  *   stores them.  The stored active sets are kept (a warm-start hint that never decides the answer; reset forgets them).
+ * set_model: new models for `count` instances, for a loop that re-estimates them: A (nx x nx x count) and B (nx x nu x count),
+ *   instance-minor over the UPDATE -- A[(r*nx + c)*count + j], B[(r*nu + k)*count + j] belong to instance idx[j].  idx == NULL means
+ *   instances 0..count-1 in order and needs count == Bsz (every model replaced); count == 0 does nothing and returns 0.  The entries
+ *   of idx are distinct and lie in [0, Bsz): the host flavour checks that, before anything is enqueued (LQMPC_ERR_BAD_ARG); the
+ *   device flavour cannot, and its kernels skip an entry outside [0, Bsz), so a bad index never writes outside the controller.  Every
+ *   later step of a listed instance is the QP of the new (A, B) under the controller's Q, R, P, box and current references (those of
+ *   the last set_reference); an unlisted instance keeps every bit of its record, its copies of A and B and its stored active set.
+ *   The stored active sets of the listed instances are kept as well, as set_reference keeps them.  The records of the listed
+ *   instances are rewritten by the factor launch of create, run over the update as a batch of `count` and redirected through idx;
+ *   lqmpc_ctl_scatter_model_kernel refreshes the controller's copies of A and B (all a pass-through controller has).  Enqueued on
+ *   the handle's stream: behind earlier steps, in front of later ones.  set_model has copied its arrays when it returns (it waits for
+ *   the stream, as create does); set_model_dev returns at once, allocates nothing, and dA, dB, didx stay the caller's to keep alive
+ *   until the stream has passed, as with step_dev.  Non-finite entries behave as at create: status 2 at those instances' steps.
  * lqmpc_jit_compile_controller: the two kernels (factor, step) of a shape without prebuilt ones, compiled (or found in the cache
  *   directory) now; needs no GPU; returns 2 or a negative lqmpc_error. */
 typedef struct lqmpc_controller lqmpc_controller;
@@ -324,6 +337,8 @@ int lqmpc_controller_step(lqmpc_controller *c, const double *x, double *u0, doub
 int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, int32_t *dstatus, int32_t *diters);
 int lqmpc_controller_reset(lqmpc_controller *c);
 int lqmpc_controller_set_reference(lqmpc_controller *c, const double *x_ref, const double *u_ref);
+int lqmpc_controller_set_model(lqmpc_controller *c, int64_t count, const int32_t *idx, const double *A, const double *B);
+int lqmpc_controller_set_model_dev(lqmpc_controller *c, int64_t count, const int32_t *didx, const double *dA, const double *dB);
 int64_t lqmpc_controller_bytes(const lqmpc_controller *c);
 const char *lqmpc_controller_kernel(const lqmpc_controller *c);
 int lqmpc_controller_destroy(lqmpc_controller *c);

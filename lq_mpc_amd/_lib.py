@@ -30,7 +30,8 @@ EXPORTS = [
     "lqmpc_timer_begin", "lqmpc_timer_end",
     "lqmpc_jit_cache_dir", "lqmpc_jit_compile", "lqmpc_jit_compile_bounds",
     "lqmpc_controller_create", "lqmpc_controller_create_dev", "lqmpc_controller_step", "lqmpc_controller_step_dev",
-    "lqmpc_controller_reset", "lqmpc_controller_set_reference", "lqmpc_controller_bytes", "lqmpc_controller_kernel", "lqmpc_controller_destroy",
+    "lqmpc_controller_reset", "lqmpc_controller_set_reference",
+    "lqmpc_controller_set_model", "lqmpc_controller_set_model_dev", "lqmpc_controller_bytes", "lqmpc_controller_kernel", "lqmpc_controller_destroy",
     "lqmpc_jit_compile_controller",
 ]
 
@@ -114,6 +115,8 @@ def lib():
     L.lqmpc_controller_step_dev.argtypes = [_H] + [P] * 5
     L.lqmpc_controller_reset.argtypes = [_H]
     L.lqmpc_controller_set_reference.argtypes = [_H, P, P]
+    L.lqmpc_controller_set_model.argtypes = [_H, ctypes.c_int64, P, P, P]
+    L.lqmpc_controller_set_model_dev.argtypes = [_H, ctypes.c_int64, P, P, P]
     L.lqmpc_controller_bytes.argtypes = [_H]
     L.lqmpc_controller_bytes.restype = ctypes.c_int64
     L.lqmpc_controller_kernel.argtypes = [_H]

@@ -1204,6 +1204,7 @@ void ctl_bind(const lqmpc_controller *c, KParams &p)
     p.ctl_rec = (double *)c->rec;
     p.ctl_stride = c->wg ? lqmpc::wg_ctl_rec_layout(c->nx, c->nu, c->N).stride : lqmpc::ctl_rec_layout(c->nx, c->nu, c->N).stride;
     p.ctl_face = (unsigned long long *)c->face;
+    p.ctl_idx = nullptr; p.ctl_n = c->Bsz;
 }
 
 int ctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B, hipMemcpyKind kind, const double *Q,
@@ -1382,6 +1383,75 @@ int lqmpc_controller_set_reference(lqmpc_controller *c, const double *x_ref, con
         return fail(LQMPC_ERR_HIP, "controller retarget kernel launch failed");
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+// New models for `count` instances (the update's arrays instance-minor over count): the controller's copies of A and B, then the
+// factor launch of create over the update as if it were a batch of count instances, its records redirected through didx.  Everything
+// is enqueued on the handle's stream; nothing is allocated and nothing waits.
+int lqmpc_controller_set_model_dev(lqmpc_controller *c, int64_t count, const int32_t *didx, const double *dA, const double *dB)
+{
+    if (!c) return fail(LQMPC_ERR_BAD_ARG, "controller is NULL");
+    if (count == 0) return 0;
+    if (count < 0 || count > c->Bsz) return fail(LQMPC_ERR_BAD_ARG, "count must be in [0, Bsz]");
+    if (!didx && count != c->Bsz) return fail(LQMPC_ERR_BAD_ARG, "idx == NULL replaces every model: count must equal Bsz");
+    if (!dA || !dB) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    const int nx = c->nx, nu = c->nu;
+    // the plan and the shared block of the controller's own batch, as at create and at every step: the factor launch is sized by
+    // p.Bsz alone and takes nothing from the plan, so a small update runs the kernel the whole batch was factored by.  The shared
+    // block holds the references last given by set_reference: v_r of the rewritten records is computed from those.
+    KParams p;
+    Plan pl;
+    int rc = c->fast ? prepare(h, c->opt, ctl_call(c), p, pl) : 0;
+    if (rc) return rc;
+    if (c->A) {
+        // (a workgroup-record controller keeps no copies: its records hold A and B)
+        if (didx) lqmpc::launch_ctl_scatter_model((double *)c->A, (double *)c->B, dA, dB, didx, nx, nu, count, c->Bsz, h->stream);
+        else {
+            const size_t b = (size_t)c->Bsz;
+            HIP_TRY(hipMemcpyAsync(c->A, dA, b * nx * nx * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(c->B, dB, b * nx * nu * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (!c->fast) return 0;
+    ctl_bind(c, p);
+    p.A = dA; p.B = dB; p.Bsz = count;
+    p.ctl_idx = didx;
+    p.mode = lqmpc::MODE_CTL_FACTOR;
+    return ctl_launch(c, p);
+}
+
+int lqmpc_controller_set_model(lqmpc_controller *c, int64_t count, const int32_t *idx, const double *A, const double *B)
+{
+    if (!c) return fail(LQMPC_ERR_BAD_ARG, "controller is NULL");
+    if (count == 0) return 0;
+    if (count < 0 || count > c->Bsz) return fail(LQMPC_ERR_BAD_ARG, "count must be in [0, Bsz]");
+    if (!idx && count != c->Bsz) return fail(LQMPC_ERR_BAD_ARG, "idx == NULL replaces every model: count must equal Bsz");
+    if (!A || !B) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (idx) {
+        // distinct and in range, before anything is enqueued
+        std::vector<char> seen((size_t)c->Bsz, 0);
+        for (int64_t j = 0; j < count; ++j) {
+            if (idx[j] < 0 || idx[j] >= c->Bsz) return fail(LQMPC_ERR_BAD_ARG, "idx holds an instance outside [0, Bsz)");
+            if (seen[(size_t)idx[j]]) return fail(LQMPC_ERR_BAD_ARG, "idx holds an instance twice");
+            seen[(size_t)idx[j]] = 1;
+        }
+    }
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t m = (size_t)count, nx = (size_t)c->nx, nu = (size_t)c->nu;
+    s.begin(m * (8 * (nx * nx + nx * nu) + 4));
+    const int32_t *didx = s.in(idx, m);
+    const double *dA = s.in(A, m * nx * nx), *dB = s.in(B, m * nx * nu);
+    s.upload();
+    if (s.rc) return s.rc;
+    int rc = lqmpc_controller_set_model_dev(c, count, didx, dA, dB);
+    if (rc) return rc;
+    // the staging is the handle's and the caller may overwrite A, B and idx as soon as this returns: wait, as create does
+    return s.finish();
 }
 
 int64_t lqmpc_controller_bytes(const lqmpc_controller *c) { return c ? (int64_t)c->bytes : 0; }

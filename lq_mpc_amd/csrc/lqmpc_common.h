@@ -62,6 +62,9 @@ struct KParams {
     long long ctl_stride;                 // ... doubles from one record to the next
     unsigned long long *ctl_face;         // MODE_CTL_STEP, per instance (2 + 2 nx words): the active set of the previous step (lower, upper; 0 = none),
                                           // the state it was found at, the state the model expected next
+    const int *ctl_idx;                   // MODE_CTL_FACTOR over an update (lqmpc_controller_set_model): instance j of the launch (A, B, Bsz
+                                          // are the update's) writes record ctl_idx[j]; null = record j.  An entry outside [0, ctl_n) is skipped
+    long long ctl_n;                      // ... records the controller holds
 };
 
 // One record of a prepared controller, in doubles: [A | B | G | v_r] (what every step reads) then [W] then [P] (what only the active-set

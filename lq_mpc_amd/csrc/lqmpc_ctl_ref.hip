@@ -1,5 +1,6 @@
 // lqmpc_ctl_ref.hip -- new references for a prepared controller (lqmpc_controller_set_reference, include/lqmpc.h): the two kernels that
-// rewrite v_r in the records, one per record layout.
+// rewrite v_r in the records, one per record layout.  At the end of the file: lqmpc_ctl_scatter_model_kernel, the part of
+// lqmpc_controller_set_model that refreshes the controller's instance-minor copies of A and B.
 //
 // Of a record [A | B | G | v_r | W | P] only v_r depends on the references:
 //   v_r = -W (2 gref + P centre) = -2 W gref - centre,
@@ -206,6 +207,31 @@ bool launch_wg_ctl_retarget(const KParams &p, hipStream_t stream)
     }
     hipLaunchKernelGGL(lqmpc_wg_ctl_retarget_kernel, dim3((unsigned)p.Bsz), dim3(256), bytes, stream, p);
     return true;
+}
+
+// ---- new models for listed instances (lqmpc_controller_set_model): the controller's instance-minor copies of A and B ----
+// Element (e, j) of the update's arrays (instance-minor over the update: e * count + j) goes to e * Bsz + idx[j] of the copies: rows
+// e < nA belong to A, the nB rows behind them to B.  Lane = j, one 8-byte element per lane: the reads are coalesced, the writes land
+// wherever the list sends them.  An index outside [0, Bsz) writes nothing.
+constexpr int SCATTER_WG = 256;
+
+__global__ void __launch_bounds__(SCATTER_WG) lqmpc_ctl_scatter_model_kernel(double *A, double *B, const double *uA, const double *uB,
+                                                                             const int *idx, int nA, int nB, long long count, long long Bsz)
+{
+    const long long j = (long long)blockIdx.x * SCATTER_WG + threadIdx.x;
+    if (j >= count) return;
+    const long long b = idx[j];
+    if ((unsigned long long)b >= (unsigned long long)Bsz) return;
+    const int e = blockIdx.y;                // (grid.y = nA + nB)
+    if (e < nA) A[(long long)e * Bsz + b] = uA[(long long)e * count + j];
+    else B[(long long)(e - nA) * Bsz + b] = uB[(long long)(e - nA) * count + j];
+}
+
+void launch_ctl_scatter_model(double *A, double *B, const double *uA, const double *uB, const int *idx, int nx, int nu, long long count,
+                              long long Bsz, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((count + SCATTER_WG - 1) / SCATTER_WG), (unsigned)(nx * nx + nx * nu));
+    hipLaunchKernelGGL(lqmpc_ctl_scatter_model_kernel, grid, dim3(SCATTER_WG), 0, stream, A, B, uA, uB, idx, nx * nx, nx * nu, count, Bsz);
 }
 
 }  // namespace lqmpc

@@ -53,5 +53,9 @@ bool launch_ctl(const KParams &p, hipStream_t stream, const char **name);
 // (p.sh, p.has_ref) and the record's own A, B, W; run-time dimensions, so the run-time compiled shapes are served as well
 bool launch_ctl_retarget(const KParams &p, hipStream_t stream);          // ctl_rec_layout records
 bool launch_wg_ctl_retarget(const KParams &p, hipStream_t stream);       // wg_ctl_rec_layout records
+// ... and new models for listed instances: the update's arrays (instance-minor over `count`) scattered into the controller's
+// instance-minor copies at the columns idx[0..count) (device); an index outside [0, Bsz) writes nothing
+void launch_ctl_scatter_model(double *A, double *B, const double *uA, const double *uB, const int *idx, int nx, int nu, long long count,
+                              long long Bsz, hipStream_t stream);
 
 }  // namespace lqmpc

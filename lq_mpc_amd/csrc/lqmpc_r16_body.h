@@ -354,9 +354,11 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
     }
     if constexpr (CTL_F) {
         // the record of my instance: [A | B | G | v_r | W | P], the triangles element by element over the lanes of the instance
+        // (a launch over an update, lqmpc_controller_set_model: instance b of the update's arrays is record ctl_idx[b] of the controller)
         __syncthreads();
-        if (valid) {
-            double *rc = p.ctl_rec + b * p.ctl_stride;
+        const long long ir = p.ctl_idx ? (long long)p.ctl_idx[b] : b;
+        if (valid && (unsigned long long)ir < (unsigned long long)p.ctl_n) {
+            double *rc = p.ctl_rec + ir * p.ctl_stride;
             for (int e = i; e < NX * NX; e += LPI) rc[CR::oA + e] = p.A[(long long)e * Bsz + b];
             for (int e = i; e < NX * NU; e += LPI) rc[CR::oB + e] = p.B[(long long)e * Bsz + b];
 #pragma unroll

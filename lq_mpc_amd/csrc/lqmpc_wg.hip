@@ -1295,9 +1295,12 @@ __global__ void __launch_bounds__(256, 1) lqmpc_wg_ctl_factor_kernel(KParams p)
     const long long b = blockIdx.x;
     const int nx = p.nx, nu = p.nu, N = p.N, n = p.n;
     Wg w{p, wg_offsets(nx, nu, N), lds, n, (n + BS - 1) / BS, ((n + BS - 1) / BS) * BS, nx, nu, N, (int)threadIdx.x};
+    // a launch over an update (lqmpc_controller_set_model): block b sets up from the update's arrays and stores at record ctl_idx[b]
+    const long long ir = p.ctl_idx ? (long long)p.ctl_idx[b] : b;
+    if ((unsigned long long)ir >= (unsigned long long)p.ctl_n) return;       // (the whole block: an index the caller should not have sent)
     w.init_rows();
     w.setup(b);
-    w.store_record(p.ctl_rec + b * p.ctl_stride, wg_ctl_rec_layout(nx, nu, N));
+    w.store_record(p.ctl_rec + ir * p.ctl_stride, wg_ctl_rec_layout(nx, nu, N));
 }
 
 // Per instance in p.ctl_face, (4 + 2 nx) words: the face the previous step ended on (WG_CTL_FACE_WORDS row masks), the state it was

@@ -72,6 +72,34 @@ def _ref_or_none(r, rows, N):
     return r if np.any(r) else None
 
 
+
+def _model_update_args(nx, nu, Bsz, A, B, idx):
+    """The host arguments of BatchController.set_model, checked before the library sees them: A (nx, nx, m) and B (nx, nu, m)
+    float64, idx None (then m == Bsz) or m distinct integers in [0, Bsz).  Returns (A, B, idx as int32 or None, m)."""
+    A, B = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(B, dtype=np.float64)
+    if A.ndim != 3 or A.shape[:2] != (nx, nx):
+        raise ValueError(f"A must be ({nx}, {nx}, m), got {A.shape}")
+    m = A.shape[2]
+    if B.shape != (nx, nu, m):
+        raise ValueError(f"B must be ({nx}, {nu}, {m}), got {B.shape}")
+    if idx is None:
+        if m != Bsz:
+            raise ValueError(f"idx=None replaces every model: m must be Bsz = {Bsz}, got {m}")
+        return A, B, None, m
+    idx = np.asarray(idx)
+    if idx.size == 0:
+        idx = idx.astype(np.int64)                           # (an empty list has no integer type of its own)
+    if idx.ndim != 1 or not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError("idx must be a one-dimensional sequence of integers")
+    if idx.size != m:
+        raise ValueError(f"idx names {idx.size} instances, A and B hold {m}")
+    if m and (idx.min() < 0 or idx.max() >= Bsz):
+        raise ValueError(f"idx must lie in [0, {Bsz})")
+    if np.unique(idx).size != m:
+        raise ValueError("idx must not name an instance twice")
+    return A, B, np.ascontiguousarray(idx, dtype=np.int32), m
+
+
 class BatchSolver:
     """One handle = one GPU + one stream (include/lqmpc.h).  Not thread-safe."""
 
@@ -354,6 +382,33 @@ class BatchController:
         c = self._live()
         x_ref, u_ref = _ref_or_none(x_ref, self.nx, self.N), _ref_or_none(u_ref, self.nu, self.N)
         _lib.check(self._L.lqmpc_controller_set_reference(c, _ptr(x_ref), _ptr(u_ref)))
+
+    def set_model(self, A, B, idx=None):
+        """New models for some or all instances, in place: A (nx, nx, m), B (nx, nu, m), instance-minor over the update, for the
+        instances idx (m distinct integers in [0, Bsz); None: all of them in order, m == Bsz).  Numpy arrays: checked here, copied
+        before this returns.  Device tensors (.shape, .data_ptr(), contiguous float64; idx an int32 device tensor of length m or
+        None): enqueued like a step, returns at once, the caller keeps them alive until the stream has passed and answers for
+        "distinct and in range".  Listed instances step with the new model under the current references; the others keep every
+        bit, and all carried active sets are kept (reset() forgets them)."""
+        c = self._live()
+        if hasattr(A, "data_ptr") != hasattr(B, "data_ptr"):
+            raise ValueError("A and B must both be numpy arrays or both be device tensors")
+        if not hasattr(A, "data_ptr"):
+            A, B, idx, m = _model_update_args(self.nx, self.nu, self.Bsz, A, B, idx)
+            _lib.check(self._L.lqmpc_controller_set_model(c, m, _ptr(idx), _ptr(A), _ptr(B)))
+            return
+        sa, sb = tuple(A.shape), tuple(B.shape)
+        if len(sa) != 3 or sa[:2] != (self.nx, self.nx) or sb != (self.nx, self.nu, sa[2]):
+            raise ValueError(f"A must be ({self.nx}, {self.nx}, m) and B ({self.nx}, {self.nu}, m), got {sa} and {sb}")
+        if not (A.is_contiguous() and B.is_contiguous()) or "float64" not in str(A.dtype) or "float64" not in str(B.dtype):
+            raise ValueError("device A and B must be contiguous float64")
+        m = sa[2]
+        if idx is None:
+            if m != self.Bsz:
+                raise ValueError(f"idx=None replaces every model: m must be Bsz = {self.Bsz}, got {m}")
+        elif not hasattr(idx, "data_ptr") or tuple(idx.shape) != (m,) or "int32" not in str(idx.dtype) or not idx.is_contiguous():
+            raise ValueError(f"with device A and B, idx must be a contiguous int32 device tensor of length {m}")
+        _lib.check(self._L.lqmpc_controller_set_model_dev(c, m, _ptr(idx), _ptr(A), _ptr(B)))
 
     @property
     def kernel(self):

@@ -11,7 +11,12 @@ and after reset() (cold; the figure includes the reset's fill of the stored face
     python tools/controller_time.py --retarget [--config 3|5]
 New references in every call (two sets taken in turn, default mix): set_reference alone, set_reference + step with the face kept,
 set_reference + reset + step, destroy + create + step, and the one-shot solve with the same references; the result is kept under
-"C<config>" in profiles/controller_retarget.json."""
+"C<config>" in profiles/controller_retarget.json.
+
+    python tools/controller_time.py --set-model [--config 3|5]
+New models in place (BatchController.set_model, device flavour) against re-creating the controller: set_model of every instance
++ step, destroy + create + step, set_model alone for all, 4 096 and 64 listed instances, and the plain step; kept under "C<config>"
+in profiles/controller_set_model.json."""
 import argparse
 import json
 import os
@@ -31,8 +36,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file (default for --config 5: profiles/controller_c5.json)")
     ap.add_argument("--retarget", action="store_true", help="time set_reference against re-creating the controller and against a one-shot solve")
+    ap.add_argument("--set-model", action="store_true", help="time set_model against re-creating the controller")
     a = ap.parse_args()
-    if a.out is None and a.config == 5 and not a.retarget:
+    if a.out is None and a.config == 5 and not a.retarget and not a.set_model:
         a.out = os.path.join(ROOT, "profiles", "controller_c5.json")
     import torch
     from lq_mpc_amd import BatchController, BatchSolver, synth
@@ -43,6 +49,9 @@ def main():
     out = {"tool": "controller_time", "config": a.config, "calls": a.calls, "rounds": a.rounds, "device": torch.cuda.get_device_name(0)}
     if a.retarget:
         retarget(a, s, out, torch)
+        return
+    if a.set_model:
+        set_model(a, s, out, torch)
         return
     for mix in ("default", "hard"):
         b = synth.make_batch(a.config, mix=mix)
@@ -152,6 +161,62 @@ def retarget(a, s, out, torch):
     s.close()
     path = a.out or os.path.join(ROOT, "profiles", "controller_retarget.json")
     allr = json.load(open(path)) if os.path.exists(path) else {"tool": "controller_time --retarget"}
+    allr[f"C{a.config}"] = res
+    print(json.dumps({f"C{a.config}": res}))
+    with open(path, "w") as f:
+        f.write(json.dumps(allr, indent=1) + "\n")
+
+
+def set_model(a, s, out, torch):
+    from lq_mpc_amd import BatchController, synth
+    b = synth.make_batch(a.config)
+    nx, nu, Bsz = b["B"].shape
+    N = b["N"]
+    dev = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()
+    dA, dB, dx = dev(b["A"]), dev(b["B"]), dev(b["x0"])
+    du = torch.empty((nu, Bsz), dtype=torch.float64, device="cuda")
+    dv = torch.empty(Bsz, dtype=torch.float64, device="cuda")
+    part = {}
+    for m in (4096, 64):
+        idx = np.random.default_rng(m).permutation(Bsz)[:m]
+        part[m] = (dev(b["A"][..., idx]), dev(b["B"][..., idx]), dev(idx.astype(np.int32)))
+    torch.cuda.synchronize()
+    s.reserve(nx, nu, N, Bsz)
+    fixed = (b["Q"], b["R"], b["P"], b["lb"], b["ub"])
+    ctl = [BatchController(s, N, dA, dB, *fixed)]
+
+    def timed(body):
+        s.timer_begin()
+        for _ in range(a.calls):
+            body()
+        return s.timer_end() / a.calls
+
+    def update_step():
+        ctl[0].set_model(dA, dB)
+        ctl[0].step_dev(dx, du, dv)
+
+    def recreate():
+        ctl[0].close()
+        ctl[0] = BatchController(s, N, dA, dB, *fixed)
+        ctl[0].step_dev(dx, du, dv)
+
+    legs = {"t_set_model_all_step_ms": update_step,
+            "t_destroy_create_step_ms": recreate,
+            "t_set_model_all_ms": lambda: ctl[0].set_model(dA, dB),
+            "t_set_model_4096_ms": lambda: ctl[0].set_model(*part[4096]),
+            "t_set_model_64_ms": lambda: ctl[0].set_model(*part[64]),
+            "t_step_ms": lambda: ctl[0].step_dev(dx, du, dv)}
+    for _ in range(3):
+        for f in legs.values():
+            timed(f)
+    r = [{k: timed(f) for k, f in legs.items()} for _ in range(a.rounds)]
+    res = {k: round(float(np.median([q[k] for q in r])), 5) for k in legs}
+    res.update(shape=[nx, nu, N], Bsz=Bsz, kernel=ctl[0].kernel, bytes_per_instance=ctl[0].nbytes / Bsz, device=out["device"], calls=a.calls,
+               rounds=a.rounds)
+    ctl[0].close()
+    s.close()
+    path = a.out or os.path.join(ROOT, "profiles", "controller_set_model.json")
+    allr = json.load(open(path)) if os.path.exists(path) else {"tool": "controller_time --set-model"}
     allr[f"C{a.config}"] = res
     print(json.dumps({f"C{a.config}": res}))
     with open(path, "w") as f:
