@@ -320,8 +320,25 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
  *   the handle's stream: behind earlier steps, in front of later ones.  set_model has copied its arrays when it returns (it waits for
  *   the stream, as create does); set_model_dev returns at once, allocates nothing, and dA, dB, didx stay the caller's to keep alive
  *   until the stream has passed, as with step_dev.  Non-finite entries behave as at create: status 2 at those instances' steps.
+ * rollout: T closed-loop steps of every instance from the controller's present state, in one launch -- what lqmpc_rollout_batch[_dev]
+ *   returns for the controller's models (every set_model so far), its Q, R, P and box and the references of the last
+ *   set_reference, without rebuilding the set-up the records already hold.  x0, JT, X, U, status, iters and A_true / B_true /
+ *   true_per_instance are laid out and mean what they do for lqmpc_rollout_batch: a shared plant is a HOST pointer in both flavours,
+ *   a per-instance plant a host pointer in the host flavour and a device pointer in _dev.  X, U, status, iters may be NULL.
+ *   T < 1 (or > 100000) or a NULL c, x0, A_true, B_true or JT gives LQMPC_ERR_BAD_ARG before anything is enqueued.  A rollout is
+ *   read-only on the controller: it starts cold, with empty faces, as lqmpc_rollout_batch does, carries its own face from step to
+ *   step inside the kernel, neither reads nor writes the stored active sets and does not touch the records, so the steps before
+ *   and after it are bit for bit what they would be without it.  Enqueued on the handle's stream, ordered with steps, set_reference
+ *   and set_model; _dev returns at once, the host flavour copies in and out and waits, as step does.  It sets the handle's
+ *   lqmpc_last_kernel: lqmpc_ctl_roll_r16_kernel<..> / lqmpc_ctl_roll_r64_kernel<..> / lqmpc_wg_ctl_rollout_kernel on a record
+ *   controller (G and v_r from the record, W the first time an instance leaves the box, P the first time an iteration takes the
+ *   primal side; an instance that reaches r16_maxit is redone by the hand-back pass of lqmpc_rollout_batch_dev from the
+ *   controller's copies of A and B).  A pass-through controller runs lqmpc_rollout_batch_dev under its option snapshot on its
+ *   copies of A and B; so does a 16-lane-row record controller of 4 096 instances or more, where the record kernel
+ *   measured no faster than the one-shot call with its difficulty order (profiles/controller_rollout.json).
  * lqmpc_jit_compile_controller: the two kernels (factor, step) of a shape without prebuilt ones, compiled (or found in the cache
- *   directory) now; needs no GPU; returns 2 or a negative lqmpc_error. */
+ *   directory) now; needs no GPU; returns 2 or a negative lqmpc_error.  lqmpc_jit_compile_controller_rollout: likewise the rollout
+ *   kernel; returns 1, or LQMPC_ERR_UNSUPPORTED outside the 16-lane-row domain. */
 typedef struct lqmpc_controller lqmpc_controller;
 int lqmpc_controller_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
                             const double *A, const double *B,
@@ -335,6 +352,12 @@ int lqmpc_controller_create_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t 
                                 const double *x_ref, const double *u_ref, lqmpc_controller **out);
 int lqmpc_controller_step(lqmpc_controller *c, const double *x, double *u0, double *VN, int32_t *status, int32_t *iters);
 int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, int32_t *dstatus, int32_t *diters);
+int lqmpc_controller_rollout(lqmpc_controller *c, int T, const double *x0,
+                             const double *A_true, const double *B_true, int true_per_instance,
+                             double *JT, double *X, double *U, int32_t *status, int32_t *iters);
+int lqmpc_controller_rollout_dev(lqmpc_controller *c, int T, const double *dx0,
+                                 const double *A_true, const double *B_true, int true_per_instance,
+                                 double *dJT, double *dX, double *dU, int32_t *dstatus, int32_t *diters);
 int lqmpc_controller_reset(lqmpc_controller *c);
 int lqmpc_controller_set_reference(lqmpc_controller *c, const double *x_ref, const double *u_ref);
 int lqmpc_controller_set_model(lqmpc_controller *c, int64_t count, const int32_t *idx, const double *A, const double *B);
@@ -343,6 +366,7 @@ int64_t lqmpc_controller_bytes(const lqmpc_controller *c);
 const char *lqmpc_controller_kernel(const lqmpc_controller *c);
 int lqmpc_controller_destroy(lqmpc_controller *c);
 int lqmpc_jit_compile_controller(int nx, int nu, int N, char *log, int log_len);
+int lqmpc_jit_compile_controller_rollout(int nx, int nu, int N, char *log, int log_len);
 
 /* ---- timing on the handle's stream (hipEvents), for bench.py's roofline ----
  * begin/end bracket any number of *_dev calls; end waits for the stream and returns the

@@ -33,6 +33,7 @@ EXPORTS = [
     "lqmpc_controller_reset", "lqmpc_controller_set_reference",
     "lqmpc_controller_set_model", "lqmpc_controller_set_model_dev", "lqmpc_controller_bytes", "lqmpc_controller_kernel", "lqmpc_controller_destroy",
     "lqmpc_jit_compile_controller",
+    "lqmpc_controller_rollout", "lqmpc_controller_rollout_dev", "lqmpc_jit_compile_controller_rollout",
 ]
 
 
@@ -113,6 +114,10 @@ def lib():
     L.lqmpc_controller_create_dev.argtypes = ctl_create_args
     L.lqmpc_controller_step.argtypes = [_H] + [P] * 5
     L.lqmpc_controller_step_dev.argtypes = [_H] + [P] * 5
+    ctl_roll_args = [_H, ctypes.c_int, P, P, P, ctypes.c_int] + [P] * 5
+    L.lqmpc_controller_rollout.argtypes = ctl_roll_args
+    L.lqmpc_controller_rollout_dev.argtypes = ctl_roll_args
+    L.lqmpc_jit_compile_controller_rollout.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
     L.lqmpc_controller_reset.argtypes = [_H]
     L.lqmpc_controller_set_reference.argtypes = [_H, P, P]
     L.lqmpc_controller_set_model.argtypes = [_H, ctypes.c_int64, P, P, P]
@@ -152,6 +157,15 @@ def jit_compile_controller(nx, nu, N):
     rc = lib().lqmpc_jit_compile_controller(int(nx), int(nu), int(N), log, len(log))
     if rc < 0:
         raise LqmpcError(f"lqmpc_jit_compile_controller({nx},{nu},{N}) -> {rc}: {log.value.decode(errors='replace')}")
+    return rc
+
+
+def jit_compile_controller_rollout(nx, nu, N):
+    """The rollout kernel of a prepared controller for one shape, compiled (or found in the cache) now; needs no GPU."""
+    log = ctypes.create_string_buffer(4096)
+    rc = lib().lqmpc_jit_compile_controller_rollout(int(nx), int(nu), int(N), log, len(log))
+    if rc < 0:
+        raise LqmpcError(f"lqmpc_jit_compile_controller_rollout({nx},{nu},{N}) -> {rc}: {log.value.decode(errors='replace')}")
     return rc
 
 

@@ -701,6 +701,29 @@ static int solve_dev(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, c
     return pl.rows() ? launch_rows(h, pl, p) : launch(h, pl, p);
 }
 
+// lqmpc_rollout_batch_dev under explicit options (a prepared controller passes through here under its own snapshot)
+static int rollout_dev(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, const double *dA, const double *dB, const double *dx0,
+                       const double *A_true, const double *B_true, double *dJT, double *dX, double *dU, int32_t *dstatus, int32_t *diters)
+{
+    KParams p;
+    Plan pl;
+    int rc = prepare(h, opt, c, p, pl);
+    if (rc) return rc;
+    p.A = dA; p.B = dB; p.x0 = dx0; p.JT = dJT; p.X = dX; p.U = dU; p.status = dstatus; p.iters = diters;
+    if (c.true_per_instance) { p.At = A_true; p.Bt = B_true; }
+    if (pl.order) {
+        rc = build_order(h, pl, p);
+        if (rc) return rc;
+    }
+    if (pl.rows()) return launch_rows(h, pl, p);
+    if (pl.family != FAM_SPEC_TIERED) return launch(h, pl, p);
+    p.nwide = pl.nwide;
+    rc = prepare_hand_back(h, p);
+    if (!rc) rc = launch(h, pl, p);
+    // second pass: whatever the wide tier handed back (status 3), packed, from the start of the rollout
+    return rc ? rc : launch_hand_back(h, pl, p, p.mode, nullptr);
+}
+
 extern "C" {
 
 int lqmpc_reserve(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T)
@@ -741,25 +764,9 @@ int lqmpc_rollout_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
 {
     if (!h || !dA || !dB || !dx0 || !dJT || !A_true || !B_true) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
     if (T < 1 || T > 100000) return fail(LQMPC_ERR_BAD_ARG, "T must be in [1,100000]");
-    Call c{nx, nu, N, T, 0, lqmpc::MODE_ROLLOUT, true_per_instance ? 1 : 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref,
-           A_true, B_true, nullptr};
-    KParams p;
-    Plan pl;
-    int rc = prepare(h, h->opt, c, p, pl);
-    if (rc) return rc;
-    p.A = dA; p.B = dB; p.x0 = dx0; p.JT = dJT; p.X = dX; p.U = dU; p.status = dstatus; p.iters = diters;
-    if (true_per_instance) { p.At = A_true; p.Bt = B_true; }
-    if (pl.order) {
-        rc = build_order(h, pl, p);
-        if (rc) return rc;
-    }
-    if (pl.rows()) return launch_rows(h, pl, p);
-    if (pl.family != FAM_SPEC_TIERED) return launch(h, pl, p);
-    p.nwide = pl.nwide;
-    rc = prepare_hand_back(h, p);
-    if (!rc) rc = launch(h, pl, p);
-    // second pass: whatever the wide tier handed back (status 3), packed, from the start of the rollout
-    return rc ? rc : launch_hand_back(h, pl, p, p.mode, nullptr);
+    const Call c{nx, nu, N, T, 0, lqmpc::MODE_ROLLOUT, true_per_instance ? 1 : 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref,
+                 A_true, B_true, nullptr};
+    return rollout_dev(h, h->opt, c, dA, dB, dx0, A_true, B_true, dJT, dX, dU, dstatus, diters);
 }
 
 int lqmpc_max_vn_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int K, const double *dA, const double *dB,
@@ -1161,6 +1168,8 @@ struct lqmpc_controller {
     bool fast = false, jit = false;           // fast: the record kernels serve the shape (jit: compiled at run time); else pass-through
     bool wg = false;                          // fast, on the workgroup kernel's shapes (options.ctl_wg): one launch per step, no hand-back
     std::string name = "lqmpc_solve_batch_dev";
+    std::string roll_name;                    // fast: the record kernel of lqmpc_controller_rollout
+    int roll_jit = -1;                        // jit: whether that kernel could be had (-1: not asked yet; 0: the rollout passes through)
 };
 
 namespace {
@@ -1257,6 +1266,9 @@ int ctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double
         snprintf(nm, sizeof nm, "lqmpc_ctl_r%d%s_kernel<%d,%d,%d>", N * nu <= 32 ? 16 : 64, c->jit ? "_jit" : "", nx, nu, N);
         if (!c->jit && lqmpc::r16_lanes(nx, nu, N) == 64) snprintf(nm, sizeof nm, "lqmpc_ctl_r64_kernel<%d,%d,%d>", nx, nu, N);
         c->name = c->wg ? "lqmpc_wg_ctl_step_kernel" : nm;
+        snprintf(nm, sizeof nm, "lqmpc_ctl_roll_r%d%s_kernel<%d,%d,%d>", lqmpc::r16_lanes(nx, nu, N) == 64 || N * nu > 32 ? 64 : 16,
+                 c->jit ? "_jit" : "", nx, nu, N);
+        c->roll_name = c->wg ? "lqmpc_wg_ctl_rollout_kernel" : nm;
         ctl_bind(c, p);
         p.mode = lqmpc::MODE_CTL_FACTOR;
         rc = ctl_launch(c, p);
@@ -1348,6 +1360,94 @@ int lqmpc_controller_step(lqmpc_controller *c, const double *x, double *u0, doub
     int rc = lqmpc_controller_step_dev(c, dx, du0, dVN, dst, dit);
     if (rc) return rc;
     s.back(u0, du0, b * c->nu); s.back(VN, dVN, b); s.back(status, dst, b); s.back(iters, dit, b);
+    return s.finish();
+}
+
+// T closed-loop steps of every instance from the controller's present state, in one launch.  Read-only on the controller: the
+// rollout starts cold and carries its own face inside the kernel; ctl_face and the records are not written.
+//
+// Routing of a 16-lane-row record controller (the workgroup records have one kernel, 10.9 against 13.5 ms at C5 x 32 768, and no
+// copies of A, B to pass through with).  Measured on one MI355X, T = 30, default mix, record kernel against lqmpc_rollout_batch_dev
+// (profiles/controller_rollout.json, "record kernel at every size"): C3 0.176 against 0.170 ms at 4 096 instances, 0.196 / 0.218 at
+// 8 192, 0.228 / 0.217 at 16 384, 0.317 / 0.230 at 32 768, 0.488 / 0.305 at 65 536; C4 x 262 144 6.02 against 4.18 ms.  The record
+// kernel walks the batch in natural order without the set-up's cold-start guess; the one-shot call orders by difficulty from 8 192
+// instances (make_plan) and gains more from that than its set-up costs.  From the smallest size measured, 4 096, the record kernel is
+// not faster by more than the +-3 % of lease noise, so from there the rollout goes to lqmpc_rollout_batch_dev on the controller's
+// copies; below it (not measured against the one-shot call: a handful of wavefronts, where the set-up is latency on the only
+// wavefront a SIMD has) it stays on the records.
+constexpr int64_t CTL_ROLL_ROWS_MAX = 4095;
+int lqmpc_controller_rollout_dev(lqmpc_controller *c, int T, const double *dx0, const double *A_true, const double *B_true,
+                                 int true_per_instance, double *dJT, double *dX, double *dU, int32_t *dstatus, int32_t *diters)
+{
+    if (!c || !dx0 || !A_true || !B_true || !dJT) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (T < 1 || T > 100000) return fail(LQMPC_ERR_BAD_ARG, "T must be in [1,100000]");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    const int tpi = true_per_instance ? 1 : 0;
+    Call cl = ctl_call(c);
+    cl.T = T; cl.true_per_instance = tpi; cl.At_sh = A_true; cl.Bt_sh = B_true;
+    bool rec = c->fast && (c->wg || c->Bsz <= CTL_ROLL_ROWS_MAX);
+    if (rec && c->jit) {
+        if (c->roll_jit < 0) {
+            std::string why;
+            c->roll_jit = lqmpc::jit_available(h->device, c->nx, c->nu, c->N, lqmpc::MODE_CTL_ROLL, &why) ? 1 : 0;
+            if (!c->roll_jit) g_err = "run-time compile unavailable, the controller's rollout passes through to lqmpc_rollout_batch_dev: " + why;
+        }
+        rec = c->roll_jit == 1;
+    }
+    if (!rec) {
+        // pass-through: the one-shot rollout under the controller's option snapshot, on its copies of A and B, with its references
+        cl.mode = lqmpc::MODE_ROLLOUT;
+        return rollout_dev(h, c->opt, cl, (const double *)c->A, (const double *)c->B, dx0, A_true, B_true, dJT, dX, dU, dstatus, diters);
+    }
+    // planned as a step is (the family of create, no order); the shared block carries a shared plant
+    KParams p;
+    Plan pl;
+    int rc = prepare(h, c->opt, cl, p, pl);
+    if (rc) return rc;
+    ctl_bind(c, p);
+    p.ctl_face = nullptr;
+    p.x0 = dx0; p.JT = dJT; p.X = dX; p.U = dU; p.status = dstatus; p.iters = diters;
+    if (tpi) { p.At = A_true; p.Bt = B_true; }
+    p.mode = lqmpc::MODE_CTL_ROLL;
+    if (c->wg) {
+        rc = ctl_launch(c, p);
+        if (!rc) h->last_kernel = c->roll_name.c_str();
+        return rc;
+    }
+    rc = prepare_hand_back(h, p);
+    if (rc) return rc;
+    rc = ctl_launch(c, p);
+    if (rc) return rc;
+    // whatever did not settle within r16_maxit iterations at some step (or met a non-finite state): the whole rollout of that instance
+    // again on the existing kernels, over the device-side list, from the controller's copies of A and B
+    rc = launch_hand_back(h, pl, p, lqmpc::MODE_ROLLOUT, nullptr);
+    if (rc) return rc;
+    h->last_kernel = c->roll_name.c_str();
+    return 0;
+}
+
+int lqmpc_controller_rollout(lqmpc_controller *c, int T, const double *x0, const double *A_true, const double *B_true,
+                             int true_per_instance, double *JT, double *X, double *U, int32_t *status, int32_t *iters)
+{
+    if (!c || !x0 || !A_true || !B_true || !JT) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (T < 1 || T > 100000) return fail(LQMPC_ERR_BAD_ARG, "T must be in [1,100000]");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)c->Bsz, nx = (size_t)c->nx, nu = (size_t)c->nu;
+    s.begin(b * 8 * (nx * nx + nx * nu + nx + 2 + (X ? nx * (size_t)(T + 1) : 0) + (U ? nu * (size_t)T : 0)));
+    const double *dx0 = s.in(x0, b * nx);
+    const double *dAt = A_true, *dBt = B_true;
+    if (true_per_instance) { dAt = s.in(A_true, b * nx * nx); dBt = s.in(B_true, b * nx * nu); }
+    double *dJT = s.out(JT, b), *dX = s.out(X, b * nx * (size_t)(T + 1)), *dU = s.out(U, b * nu * (size_t)T);
+    int32_t *dst = s.out(status, b), *dit = s.out(iters, b);
+    s.upload();
+    if (s.rc) return s.rc;
+    int rc = lqmpc_controller_rollout_dev(c, T, dx0, dAt, dBt, true_per_instance, dJT, dX, dU, dst, dit);
+    if (rc) return rc;
+    s.back(JT, dJT, b); s.back(X, dX, b * nx * (size_t)(T + 1)); s.back(U, dU, b * nu * (size_t)T);
+    s.back(status, dst, b); s.back(iters, dit, b);
     return s.finish();
 }
 
@@ -1463,7 +1563,7 @@ int lqmpc_controller_destroy(lqmpc_controller *c)
     if (!c) return 0;
     (void)hipSetDevice(c->h->device);
     (void)hipStreamSynchronize(c->h->stream);
-    if (c->h->last_kernel == c->name.c_str()) c->h->last_kernel = "none";
+    if (c->h->last_kernel == c->name.c_str() || c->h->last_kernel == c->roll_name.c_str()) c->h->last_kernel = "none";
     ctl_free(c);
     return 0;
 }

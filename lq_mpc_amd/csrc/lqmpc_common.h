@@ -21,7 +21,9 @@ __device__ __forceinline__ void sfor(F &&f)
 
 enum Mode : int { MODE_SOLVE = 0, MODE_ROLLOUT = 1, MODE_MAXVN = 2, MODE_PROBE = 3, MODE_SWEEP = 4 /* max V_N, then the rollout */,
                   // the prepared controller (lqmpc_ctl.hip): the set-up written to one record per instance; one QP per instance from its record
-                  MODE_CTL_FACTOR = 5, MODE_CTL_STEP = 6 };
+                  MODE_CTL_FACTOR = 5, MODE_CTL_STEP = 6,
+                  // ... and T closed-loop steps per instance from its record in one launch (the rollout's loop without its set-up)
+                  MODE_CTL_ROLL = 7 };
 
 // Offsets (in doubles) into the small "shared" device block that holds the data common to the
 // whole batch: Q, R, P, lb, ub, x_ref (nx,N), u_ref (nu,N), A_true, B_true, x0s (nx,K).

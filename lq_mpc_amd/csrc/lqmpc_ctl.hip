@@ -1,4 +1,4 @@
-// lqmpc_ctl.hip -- the two kernels of a prepared controller (lqmpc_controller_*, include/lqmpc.h) in the 16-lane-row layout.
+// lqmpc_ctl.hip -- the kernels of a prepared controller (lqmpc_controller_*, include/lqmpc.h) in the 16-lane-row layout.
 //
 // A one-shot solve spends about half of its launch on what does not depend on the state: the backward Riccati sweep, W = P^-1, the
 // gain G of the unconstrained minimiser and P.  A controller runs that once (MODE_CTL_FACTOR: the set-up of lqmpc_r16_body.h as it
@@ -9,7 +9,8 @@
 // Records are instance-major and padded to 256 bytes, so the lanes of an instance read consecutive addresses.  The iterations are the
 // qp() of lqmpc_r16_body.h, not a copy; the face a step ends on is kept per instance (two 64-bit masks, with the state it was found at
 // and the state the model expected next) and warm-starts the next one: shifted by one stage as the rollout shifts it when the state
-// advanced, unshifted when it stayed.
+// advanced, unshifted when it stayed.  MODE_CTL_ROLL runs T closed-loop steps per instance from the same record (the rollout's loop
+// without its set-up; W stays in LDS once an instance has brought it in) and leaves the stored faces alone.
 #include "lqmpc_r16_body.h"
 #include "lqmpc_launch.h"
 
@@ -30,6 +31,7 @@ static void launch_ctl_one(const KParams &p, hipStream_t stream)
     constexpr int IPW = 64 / LPI;
     const dim3 grid((unsigned)((p.Bsz + IPW - 1) / IPW));
     if (p.mode == MODE_CTL_FACTOR) hipLaunchKernelGGL((lqmpc_ctl_kernel<NX, NU, N, MODE_CTL_FACTOR, LPI>), grid, dim3(64), 0, stream, p);
+    else if (p.mode == MODE_CTL_ROLL) hipLaunchKernelGGL((lqmpc_ctl_kernel<NX, NU, N, MODE_CTL_ROLL, LPI>), grid, dim3(64), 0, stream, p);
     else hipLaunchKernelGGL((lqmpc_ctl_kernel<NX, NU, N, MODE_CTL_STEP, LPI>), grid, dim3(64), 0, stream, p);
 }
 
@@ -49,11 +51,11 @@ static const ShapeEntry *find_ctl(int nx, int nu, int N)
 
 bool ctl_available(int nx, int nu, int N) { return find_ctl(nx, nu, N) != nullptr; }
 
-// p.mode: MODE_CTL_FACTOR or MODE_CTL_STEP
+// p.mode: MODE_CTL_FACTOR, MODE_CTL_STEP or MODE_CTL_ROLL
 bool launch_ctl(const KParams &p, hipStream_t stream, const char **name)
 {
     const ShapeEntry *e = find_ctl(p.nx, p.nu, p.N);
-    if (!e || (p.mode != MODE_CTL_FACTOR && p.mode != MODE_CTL_STEP)) return false;
+    if (!e || (p.mode != MODE_CTL_FACTOR && p.mode != MODE_CTL_STEP && p.mode != MODE_CTL_ROLL)) return false;
     e->launch(p, stream);
     if (name) *name = e->name;
     return true;

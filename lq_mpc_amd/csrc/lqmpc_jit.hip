@@ -213,6 +213,7 @@ static const char *mode_tag(int mode)
 {
     switch (mode) { case MODE_SOLVE: return "solve"; case MODE_ROLLOUT: return "rollout"; case MODE_MAXVN: return "maxvn";
                     case MODE_PROBE: return "probe"; case MODE_CTL_FACTOR: return "controller factor"; case MODE_CTL_STEP: return "controller step";
+                    case MODE_CTL_ROLL: return "controller rollout";
                     default: return "sweep"; }
 }
 
@@ -353,6 +354,20 @@ int lqmpc_jit_compile_controller(int nx, int nu, int N, char *log, int log_len)
         }
     }
     return 2;
+}
+
+// ... and the rollout kernel of a prepared controller (MODE_CTL_ROLL); returns 1.  (An entry point of its own: the count above is pinned.)
+int lqmpc_jit_compile_controller_rollout(int nx, int nu, int N, char *log, int log_len)
+{
+    if (log && log_len > 0) log[0] = '\0';
+    if (!lqmpc::jit_r16_shape(nx, nu, N, nullptr)) return LQMPC_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lock(lqmpc::g_mu);
+    std::string err;
+    if (!lqmpc::get_code(nx, nu, N, lqmpc::MODE_CTL_ROLL, err)) {
+        if (log && log_len > 0) snprintf(log, (size_t)log_len, "%s: %s", lqmpc::mode_tag(lqmpc::MODE_CTL_ROLL), err.c_str());
+        return LQMPC_ERR_UNSUPPORTED;
+    }
+    return 1;
 }
 
 // ... and the pair of on-chip bound-coefficient kernels of a shape (nx <= 8, nu <= 4, LDS image within 160 KiB); returns 2

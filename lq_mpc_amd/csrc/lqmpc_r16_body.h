@@ -210,11 +210,14 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
     // 0.338 -> 0.345 ms, measured with the call inside the iteration loop, outside it, and never taken).
     // The controller's step (MODE_CTL_STEP) has no set-up at all: G and v_r come from the instance's record, W when an instance of the
     // wavefront iterates, P when an iteration takes the primal side.  Its factor launch (MODE_CTL_FACTOR) always builds P.
-    constexpr bool CTL_F = MODE == MODE_CTL_FACTOR, CTL_S = MODE == MODE_CTL_STEP;
+    // Its rollout (MODE_CTL_ROLL) is the closed loop of MODE_ROLLOUT on the same record: W the first time an instance iterates, kept in
+    // LDS for the steps that follow; P the first time an iteration of the wavefront takes the primal side.
+    constexpr bool CTL_F = MODE == MODE_CTL_FACTOR, CTL_S = MODE == MODE_CTL_STEP, CTL_R = MODE == MODE_CTL_ROLL;
+    constexpr bool CTL_REC = CTL_S || CTL_R;                 // G, v_r, W and P come from the record
     using CR = CtlRecT<NX, NU, N>;
-    constexpr bool LAZY_P = (LPI == 64 && !CTL_F) || CTL_S;
+    constexpr bool LAZY_P = (LPI == 64 && !CTL_F) || CTL_REC;
     bool P_ready = !LAZY_P;
-    bool W_ready = !CTL_S;
+    bool W_ready = !CTL_REC;                 // MODE_CTL_ROLL: row-uniform, W of MY instance is in LDS
     bool face_stays = false;                 // MODE_CTL_STEP: the state did not advance since the stored face was found (set before qp())
     // row and column of element e of a packed lower triangle
     auto tri_rc = [](int e, int &r, int &c) {
@@ -228,7 +231,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
 #ifdef LQMPC_NO_ROLL                         // (dev builds: tools/prof_build.sh)
     constexpr bool ROLL = false;
 #else
-    constexpr bool ROLL = LPI == 16 && N * ((NX + 3) / 4) <= 12 && MODE != MODE_MAXVN && !CTL_F && !CTL_S;
+    constexpr bool ROLL = LPI == 16 && N * ((NX + 3) / 4) <= 12 && MODE != MODE_MAXVN && !CTL_F && !CTL_REC;
 #endif
     unsigned cold32[2] = {0u, 0u};
     bool cold_armed = false;                 // set by the caller of qp() for the QP at x0
@@ -238,7 +241,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
     long long prof_slowt = 0;
     long long prof_ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-    if constexpr (CTL_S) {
+    if constexpr (CTL_REC) {
         const double *rc = p.ctl_rec + b * p.ctl_stride;
 #pragma unroll
         for (int s = 0; s < RB; ++s) {
@@ -414,7 +417,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
     // stage weights of the open-loop value function once (the closed loop keeps its rows of them per lane, see below)
     double Qm[NX][NX], Rm[NU][NU];
     ldsd *cQ = L + C::oC, *cR = cQ + NX * NX;
-    if constexpr (MODE == MODE_ROLLOUT) {
+    if constexpr (MODE == MODE_ROLLOUT || CTL_R) {
     } else if constexpr (OCC == 2) {
         if (i == 0) {
 #pragma unroll
@@ -497,12 +500,17 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                 Lg = (ldsd *)lds_raw + gq * C::INST;
             }
             if constexpr (CTL_S) ctl_fill(Pp, CR::oP, busy);
+            else if constexpr (CTL_R) ctl_fill(Pp, CR::oP, true);       // every instance of the wavefront: P_ready holds for the later steps
             else r16_build_P<NX, NU, N, LPI, PACKED>(setup_args(p), bg, Lg, C::oP, C::oD);
             P_ready = true;
             need_P = false;
         }
         if constexpr (CTL_S) {
             if (!W_ready && __ballot(busy) != 0ull) { ctl_fill(Wp, CR::oW, busy); W_ready = true; }
+        }
+        if constexpr (CTL_R) {
+            // an instance that iterates for the first time in this rollout brings its W in; it stays for the remaining steps
+            if (__ballot(busy && !W_ready) != 0ull) { ctl_fill(Wp, CR::oW, busy && !W_ready); W_ready = W_ready || busy; }
         }
         if (__ballot(busy) != 0ull) {
 #pragma unroll 1
@@ -1015,7 +1023,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
             u[k] = ibcast<LPI>(uk, row % LPI);
         }
     };
-    if (MODE != MODE_ROLLOUT) {
+    if (MODE != MODE_ROLLOUT && !CTL_R) {
         // open loop (utils_class.py:48-91): V_N by rolling the MODEL forward with the optimal inputs
         double Am[NX][NX], Bmm[NX][NU], Pm[NX][NX];
         ldsd *cA = cR + NU * NU, *cB = cA + NX * NX, *cP = cB + NX * NU;
@@ -1169,14 +1177,17 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
             if (writer) p.MV[b] = best;
         }
     }
-    if (MODE == MODE_ROLLOUT || MODE == MODE_SWEEP) {
+    if (MODE == MODE_ROLLOUT || MODE == MODE_SWEEP || CTL_R) {
         pL = 0; pU = 0;
         // closed loop (utils_class.py:266-283).  The plant and the stage cost are spread over the lanes of the instance: lane
         // a < NX owns row a of [A_true B_true] and of Q (its state is broadcast to the others each step), lane k < NU owns row k
         // of R; the partial costs are summed over the lanes once, after the last step.
         double x[NX];
 #pragma unroll
-        for (int a = 0; a < NX; ++a) x[a] = p.rec ? p.rec[bq * REC + NX * NX + NX * NU + a] : p.x0[(long long)a * Bsz + bq];
+        for (int a = 0; a < NX; ++a) {
+            if constexpr (CTL_R) x[a] = p.x0[(long long)a * Bsz + bq];
+            else x[a] = p.rec ? p.rec[bq * REC + NX * NX + NX * NU + a] : p.x0[(long long)a * Bsz + bq];
+        }
         int ia = i < NX ? i : 0, ik = i < NU ? i : 0;
         asm volatile("" : "+v"(ia), "+v"(ik));          // (opaque: or these loads are issued at the top and their results spilled across the set-up)
         double Qr_[NX], Ar_[NX], Br_[NU], Rr_[NU];

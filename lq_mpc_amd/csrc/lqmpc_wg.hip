@@ -1286,7 +1286,7 @@ __global__ void __launch_bounds__(256, 1) lqmpc_wg_kernel(KParams p)
 
 // ---- prepared controller on this kernel's shapes: the set-up once (factor), then one QP per instance and call from its record (step) ----
 // Of a one-shot solve on these shapes the set-up is nearly everything, and nothing of it depends on the state.
-// Both kernels are built from the members of Wg; lqmpc_wg_kernel itself is not touched.  (They stand behind it: in front of it the
+// The kernels are built from the members of Wg; lqmpc_wg_kernel itself is not touched.  (They stand behind it: in front of it the
 // compiler folds one LDS address of lqmpc_wg_kernel differently.)
 __global__ void __launch_bounds__(256, 1) lqmpc_wg_ctl_factor_kernel(KParams p)
 {
@@ -1372,19 +1372,135 @@ __global__ void __launch_bounds__(256, 1) lqmpc_wg_ctl_step_kernel(KParams p)
     }
 }
 
-// p.mode: MODE_CTL_FACTOR or MODE_CTL_STEP
+// T closed-loop steps of every instance from its record, in one launch: the closed loop of lqmpc_wg_kernel's MODE_ROLLOUT branch behind
+// stage_record instead of setup().  W and P are brought in by the first step of the instance that leaves the box (a workgroup-uniform
+// flag) and stay for the rest of the rollout, so an instance whose whole rollout is interior reads [A | B | G | v_r] only.  The face is
+// carried from step to step in act_prev, as in the one-shot rollout; p.ctl_face is neither read nor written, and nothing is stored to
+// the record.  P sits in the registers from that one load, so the interior-point fall-back inside solve_qp works as in the step kernel.
+__global__ void __launch_bounds__(256, 1) lqmpc_wg_ctl_rollout_kernel(KParams p)
+{
+    extern __shared__ double lds_raw[];
+    ldsd *lds = (ldsd *)lds_raw;
+    const int t = threadIdx.x;
+    const long long b = blockIdx.x, Bsz = p.Bsz;
+    const int nx = p.nx, nu = p.nu, N = p.N, n = p.n;
+    Wg w{p, wg_offsets(nx, nu, N), lds, n, (n + BS - 1) / BS, ((n + BS - 1) / BS) * BS, nx, nu, N, t};
+    w.init_rows();
+    const WgCtlRec L = wg_ctl_rec_layout(nx, nu, N);
+    const double *rc = p.ctl_rec + b * p.ctl_stride;
+    ldsd *xs = lds + w.o.xs;
+    w.stage_record(rc, L);
+    __syncthreads();
+    if (p.true_per_instance) {                                    // the plant of my instance over the shared block's, as stage() does
+        ldsd *S = lds + w.o.SH;
+        for (int e = t; e < nx * nx; e += THREADS) S[p.so.At + e] = p.At[(long long)e * Bsz + b];
+        for (int e = t; e < nx * nu; e += THREADS) S[p.so.Bt + e] = p.Bt[(long long)e * Bsz + b];
+    }
+    if (t < nx) xs[t] = p.x0[(long long)t * Bsz + b];
+    __syncthreads();
+    const ldsd *sh = w.shd();
+    const ldsd *uu = lds + w.o.vw;
+    int iters = 0, status = 0;
+    bool have_W = false;                                          // uniform: W is in the K region and P in the registers
+    double cost = 0.0;
+    // thread i < nx carries x_i (Q x)_i of J_T, thread k < nu carries u_k (R u)_k
+    auto stage_cost = [&](bool with_u) {
+        if (t < nx) cost = __builtin_fma(xs[t], ldot(sh + p.so.Q + t * nx, 1, xs, 1, nx), cost);
+        if (with_u && t < nu) cost = __builtin_fma(uu[t], ldot(sh + p.so.R + t * nu, 1, uu, 1, nu), cost);
+    };
+    stage_cost(false);
+    if (p.X && t < nx) p.X[((long long)t * (p.T + 1)) * Bsz + b] = xs[t];
+    const int nsteps = p.T;
+    const bool chunked = nx == 8 && nu == 4 && !p.X && !p.U;
+    int kchunk = 1;
+    for (int step = 0; step < nsteps; ++step) {
+        // interior steps first (lqmpc_wg_kernel explains them): barrier-free chunks for (8,4) without trajectories, otherwise one
+        // barrier each with the next state computed speculatively into the other half of the state buffer
+        if (chunked && w.last_m > 0) {
+        } else if (chunked) {
+            const InteriorArgs ia{lds + w.o.G, sh + p.so.At, sh + p.so.Bt, sh + p.so.Q, sh + p.so.R, xs, lds + w.o.red, w.np, 0};
+            while (step < nsteps) {
+                const int kreq = kchunk < nsteps - step ? kchunk : nsteps - step;
+                InteriorArgs a2 = ia;
+                a2.par = w.R.par;
+                const InteriorRes r = interior_steps<8, 4>(a2, kreq, w.own, w.vr, w.h, w.ctr, cost);
+                w.R.par = r.par;
+                cost = r.dc;
+                step += r.f;
+                if (r.f > 0) w.act_prev = 0.0;
+                if (r.f < kreq) { kchunk = 1; break; }
+                kchunk = kchunk < 16 ? 4 * kchunk : 16;
+            }
+            if (step >= nsteps) break;
+        } else {
+            ldsd *uw = lds + w.o.vw;
+            ldsd *cur = xs, *nxt = xs + nx;
+            for (;;) {
+                double xn = 0.0;
+                const double vu = w.own ? ldot(lds + w.o.G + t, w.np, cur, 1, nx, w.vr) : 0.0;
+                if (t < nu) uw[t] = vu + w.ctr;                   // same wavefront as the readers below: LDS keeps the order
+                if (t < nx) {
+                    xn = ldot(sh + p.so.Bt + t * nu, 1, uw, 1, nu, ldot(sh + p.so.At + t * nx, 1, cur, 1, nx));
+                    nxt[t] = xn;
+                }
+                const bool out = w.own && !(fabs(vu) <= w.h);
+                if (block_any(out, w.R)) break;
+                if (t < nx) {
+                    cost = __builtin_fma(xn, ldot(sh + p.so.Q + t * nx, 1, nxt, 1, nx), cost);
+                    if (p.X) p.X[((long long)t * (p.T + 1) + step + 1) * Bsz + b] = xn;
+                }
+                if (t < nu) {
+                    const double ut = uw[t];
+                    cost = __builtin_fma(ut, ldot(sh + p.so.R + t * nu, 1, uw, 1, nu), cost);
+                    if (p.U) p.U[((long long)t * p.T + step) * Bsz + b] = ut;
+                }
+                ldsd *sw = cur; cur = nxt; nxt = sw;
+                w.act_prev = 0.0;
+                if (++step >= nsteps) break;
+            }
+            if (cur != xs) {                                      // uniform: the general path expects the state in the first half
+                __syncthreads();
+                if (t < nx) xs[t] = cur[t];
+                __syncthreads();
+            }
+            if (step >= nsteps) break;
+        }
+        // the general path: this step leaves the box (or holds a NaN)
+        if (!have_W) { w.load_W_P(rc, L); have_W = true; }
+        const int st = w.solve_qp(iters);
+        status = st > status ? st : status;
+        __syncthreads();
+        ldsd *uw = lds + w.o.vw;
+        if (t < nu) uw[t] = fmin(fmax(w.v, -w.h), w.h) + w.ctr;
+        double xn = 0.0;
+        if (t < nx) xn = ldot(sh + p.so.Bt + t * nu, 1, uw, 1, nu, ldot(sh + p.so.At + t * nx, 1, xs, 1, nx));
+        if (t < nx) xs[t] = xn;
+        stage_cost(true);
+        if (p.X && t < nx) p.X[((long long)t * (p.T + 1) + step + 1) * Bsz + b] = xn;
+        if (p.U && t < nu) p.U[((long long)t * p.T + step) * Bsz + b] = uu[t];
+        __syncthreads();
+    }
+    cost = block_sum(cost, w.R);
+    if (t == 0) {
+        p.JT[b] = cost;
+        if (p.status) p.status[b] = status;
+        if (p.iters) p.iters[b] = iters;
+    }
+}
+
+// p.mode: MODE_CTL_FACTOR, MODE_CTL_STEP or MODE_CTL_ROLL
 bool launch_wg_ctl(const KParams &p, hipStream_t stream, const char **name)
 {
-    if (p.mode != MODE_CTL_FACTOR && p.mode != MODE_CTL_STEP) return false;
+    if (p.mode != MODE_CTL_FACTOR && p.mode != MODE_CTL_STEP && p.mode != MODE_CTL_ROLL) return false;
     const size_t bytes = wg_lds_bytes(p.nx, p.nu, p.N);
-    void (*kern)(KParams) = p.mode == MODE_CTL_FACTOR ? lqmpc_wg_ctl_factor_kernel : lqmpc_wg_ctl_step_kernel;
+    void (*kern)(KParams) = p.mode == MODE_CTL_FACTOR ? lqmpc_wg_ctl_factor_kernel : p.mode == MODE_CTL_STEP ? lqmpc_wg_ctl_step_kernel : lqmpc_wg_ctl_rollout_kernel;
     const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) {
         fprintf(stderr, "lqmpc: hipFuncSetAttribute(%zu bytes of LDS): %s\n", bytes, hipGetErrorString(e));
         return false;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)p.Bsz), dim3(256), bytes, stream, p);
-    if (name) *name = p.mode == MODE_CTL_FACTOR ? "lqmpc_wg_ctl_factor_kernel" : "lqmpc_wg_ctl_step_kernel";
+    if (name) *name = p.mode == MODE_CTL_FACTOR ? "lqmpc_wg_ctl_factor_kernel" : p.mode == MODE_CTL_STEP ? "lqmpc_wg_ctl_step_kernel" : "lqmpc_wg_ctl_rollout_kernel";
     return true;
 }
 

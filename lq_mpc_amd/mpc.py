@@ -371,6 +371,36 @@ class BatchController:
         """Device pointers / tensors; enqueued on the solver's stream, returns at once."""
         _lib.check(self._L.lqmpc_controller_step_dev(self._live(), _ptr(dx), _ptr(du0), _ptr(dVN), _ptr(dstatus), _ptr(diters)))
 
+    def rollout(self, T, x0, A_true, B_true, want_traj=False):
+        """T closed-loop steps of every instance from x0 (nx, Bsz) in one launch, from the controller's present state (its models,
+        weights, box and current references): the dict of BatchSolver.rollout_batch.  A_true (nx, nx) / B_true (nx, nu): one plant
+        for the batch; (nx, nx, Bsz) / (nx, nu, Bsz): one per instance.  Read-only on the controller: the active sets carried from
+        step to step are neither used nor changed."""
+        c, nx, nu, Bsz, T = self._live(), self.nx, self.nu, self.Bsz, int(T)
+        x0 = _f64(x0, (nx, Bsz))
+        A_true, B_true = _f64(A_true), _f64(B_true)
+        per_inst = 1 if A_true.ndim == 3 else 0
+        if per_inst:
+            A_true, B_true = _f64(A_true, (nx, nx, Bsz)), _f64(B_true, (nx, nu, Bsz))
+        else:
+            A_true, B_true = _f64(A_true, (nx, nx)), _f64(B_true, (nx, nu))
+        JT = np.empty(Bsz)
+        X = np.empty((nx, T + 1, Bsz)) if want_traj and T >= 1 else None
+        U = np.empty((nu, T, Bsz)) if want_traj and T >= 1 else None
+        status = np.empty(Bsz, dtype=np.int32); iters = np.empty(Bsz, dtype=np.int32)
+        _lib.check(self._L.lqmpc_controller_rollout(c, T, _ptr(x0), _ptr(A_true), _ptr(B_true), per_inst,
+                                                    _ptr(JT), _ptr(X), _ptr(U), _ptr(status), _ptr(iters)))
+        return {"J_T": JT, "X": X, "U": U, "status": status, "iters": iters}
+
+    def rollout_dev(self, T, dx0, A_true, B_true, dJT, dX=None, dU=None, dstatus=None, diters=None, true_per_instance=False):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once.  A shared plant (true_per_instance=False)
+        is a pair of HOST arrays (nx, nx) / (nx, nu); a per-instance plant a pair of device arrays (nx, nx, Bsz) / (nx, nu, Bsz)."""
+        if not true_per_instance:
+            A_true, B_true = _f64(A_true, (self.nx, self.nx)), _f64(B_true, (self.nx, self.nu))
+        _lib.check(self._L.lqmpc_controller_rollout_dev(self._live(), int(T), _ptr(dx0), _ptr(A_true), _ptr(B_true),
+                                                        1 if true_per_instance else 0, _ptr(dJT), _ptr(dX), _ptr(dU),
+                                                        _ptr(dstatus), _ptr(diters)))
+
     def reset(self):
         """Forget the active sets carried from the previous step: the next step starts cold."""
         _lib.check(self._L.lqmpc_controller_reset(self._live()))

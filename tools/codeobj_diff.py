@@ -4,7 +4,8 @@ Compares, kernel by kernel, the instruction text (llvm-objdump -d without addres
 resources (VGPRs, AGPRs, SGPRs, LDS, scratch) of
   * the code objects inside every csrc/*.o of the two trees, and
   * with --jit, the run-time compiled kernels of the shapes build() pre-warms: every mode of lqmpc_jit_compile (solve, rollout, max-V_N,
-    sweep, probe) and both controller modes, compiled by each tree's own library into a scratch directory (needs no GPU).
+    sweep, probe) and the controller's factor and step modes, compiled by each tree's own library into a scratch directory (needs no
+    GPU).  (The controller's rollout kernel has an entry point of its own, lqmpc_jit_compile_controller_rollout, and is not compiled here.)
 Prints one line per kernel: "identical", or the number of differing lines and the resources that moved.
 
 usage: python tools/codeobj_diff.py PARENT_TREE CANDIDATE_TREE [--jit] [--jobs 8]      (both trees built: make -C lq_mpc_amd/csrc)"""
@@ -111,12 +112,13 @@ def jit_objects(tree, work, jobs):
         subprocess.run([sys.executable, "-c", _CHILD, tree, str(nx), str(nu), str(N), str(int(ctl)), d], check=True)
         # a cached file's name is a hash (of the program text, the headers and the compiler version), so the mode is taken from the order
         # in which lqmpc_jit_compile and lqmpc_jit_compile_controller write them (JIT_MODES restates it); checked as far as it can be:
-        # the count, distinct time stamps, and the probe -- the one kernel without LDS -- where the order says it is
+        # the count, distinct time stamps, and the probe -- the one kernel launched with PROBE_WG = 256 threads -- where the order says it is
         files = sorted(glob.glob(os.path.join(d, "*.hsaco")), key=lambda f: os.stat(f).st_mtime_ns)
         stamps = [os.stat(f).st_mtime_ns for f in files]
         assert len(files) == (7 if ctl else 5) and len(set(stamps)) == len(stamps), (arg, files, stamps)
-        lds = [kernels(f)["lqmpc_jit_kernel"][1][".group_segment_fixed_size"] for f in files]
-        assert [x == "0" for x in lds] == [m == "probe" for m in JIT_MODES[:len(files)]], (arg, lds)
+        wgs = [re.search(r"\.max_flat_workgroup_size:\s*(\d+)", subprocess.run([READELF, "--notes", f], capture_output=True, text=True, check=True).stdout).group(1)
+               for f in files]
+        assert [x == "256" for x in wgs] == [m == "probe" for m in JIT_MODES[:len(files)]], (arg, wgs)
         return {((nx, nu, N), m): f for m, f in zip(JIT_MODES, files)}
     found = {}
     with ThreadPoolExecutor(jobs) as ex:

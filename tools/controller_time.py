@@ -16,7 +16,13 @@ set_reference + reset + step, destroy + create + step, and the one-shot solve wi
     python tools/controller_time.py --set-model [--config 3|5]
 New models in place (BatchController.set_model, device flavour) against re-creating the controller: set_model of every instance
 + step, destroy + create + step, set_model alone for all, 4 096 and 64 listed instances, and the plain step; kept under "C<config>"
-in profiles/controller_set_model.json."""
+in profiles/controller_set_model.json.
+
+    python tools/controller_time.py --rollout [--config 3|4|5] [--bsz 4096] [--steps 30]
+A closed loop of T steps (default mix, the batch's own plant): lqmpc_rollout_batch_dev against the controller's rollout_dev on the
+same data, measured alternately (one call per timing, three warm-up rounds, median of the rounds), and once the loop of T step_dev
+calls the rollout replaces (at one state, without a plant update: a lower bound of that loop).  Kept under "C<config>" or
+"C<config>x<bsz>" in profiles/controller_rollout.json, with the kernel each call ran."""
 import argparse
 import json
 import os
@@ -37,6 +43,9 @@ def main():
     ap.add_argument("--out", default=None, help="also write the JSON line to this file (default for --config 5: profiles/controller_c5.json)")
     ap.add_argument("--retarget", action="store_true", help="time set_reference against re-creating the controller and against a one-shot solve")
     ap.add_argument("--set-model", action="store_true", help="time set_model against re-creating the controller")
+    ap.add_argument("--rollout", action="store_true", help="time the controller's rollout against lqmpc_rollout_batch_dev")
+    ap.add_argument("--bsz", type=int, default=None, help="--rollout: instances (default: the bench's batch size of the config)")
+    ap.add_argument("--steps", type=int, default=30, help="--rollout: closed-loop steps T")
     a = ap.parse_args()
     if a.out is None and a.config == 5 and not a.retarget and not a.set_model:
         a.out = os.path.join(ROOT, "profiles", "controller_c5.json")
@@ -52,6 +61,9 @@ def main():
         return
     if a.set_model:
         set_model(a, s, out, torch)
+        return
+    if a.rollout:
+        rollout(a, s, out, torch)
         return
     for mix in ("default", "hard"):
         b = synth.make_batch(a.config, mix=mix)
@@ -219,6 +231,68 @@ def set_model(a, s, out, torch):
     allr = json.load(open(path)) if os.path.exists(path) else {"tool": "controller_time --set-model"}
     allr[f"C{a.config}"] = res
     print(json.dumps({f"C{a.config}": res}))
+    with open(path, "w") as f:
+        f.write(json.dumps(allr, indent=1) + "\n")
+
+
+def rollout(a, s, out, torch):
+    from lq_mpc_amd import BatchController, synth
+    b = synth.make_batch(a.config) if a.bsz is None else synth.make_batch(a.config, Bsz=a.bsz)
+    nx, nu, Bsz = b["B"].shape
+    N, T = b["N"], a.steps
+    dev = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()
+    dA, dB, dx = dev(b["A"]), dev(b["B"]), dev(b["x0"])
+    per = np.ndim(b["A_true"]) == 3
+    At, Bt = (dev(b["A_true"]), dev(b["B_true"])) if per else (b["A_true"], b["B_true"])
+    dJ = [torch.empty(Bsz, dtype=torch.float64, device="cuda") for _ in range(2)]
+    du = torch.empty((nu, Bsz), dtype=torch.float64, device="cuda")
+    dst = torch.empty(Bsz, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    s.reserve(nx, nu, N, Bsz, T)
+    fixed = (b["Q"], b["R"], b["P"], b["lb"], b["ub"])
+    ctl = BatchController(s, N, dA, dB, *fixed)
+    names = {}
+
+    def timed(body, calls=1):
+        s.timer_begin()
+        for _ in range(calls):
+            body()
+        return s.timer_end() / calls
+
+    def one_shot():
+        s.rollout_batch_dev(nx, nu, N, Bsz, T, dA, dB, *fixed, dx, At, Bt, dJ[0], dstatus=dst, true_per_instance=per)
+        names["one_shot"] = s.last_kernel()
+
+    def prepared():
+        ctl.rollout_dev(T, dx, At, Bt, dJ[1], dstatus=dst, true_per_instance=per)
+        names["controller"] = s.last_kernel()
+
+    def step_loop():
+        for _ in range(T):
+            ctl.step_dev(dx, du)
+
+    legs = {"t_rollout_batch_dev_ms": one_shot, "t_controller_rollout_dev_ms": prepared}
+    for _ in range(3):
+        for f in legs.values():
+            timed(f)
+    r = [{k: timed(f) for k, f in legs.items()} for _ in range(a.rounds)]
+    res = {k: round(float(np.median([q[k] for q in r])), 5) for k in legs}
+    s.sync()
+    j0, j1 = dJ[0].cpu().numpy(), dJ[1].cpu().numpy()
+    timed(step_loop)
+    res["t_step_dev_loop_ms"] = round(timed(step_loop), 5)
+    res.update(one_shot_over_controller=round(res["t_rollout_batch_dev_ms"] / res["t_controller_rollout_dev_ms"], 3),
+               max_rel_diff_J_T=float(np.max(np.abs(j0 - j1) / np.abs(j0))), status_nonzero=int((dst.cpu().numpy() != 0).sum()),
+               kernel_one_shot=names["one_shot"], kernel_controller=names["controller"], kernel_step=ctl.kernel,
+               shape=[nx, nu, N], Bsz=Bsz, T=T, plant="per instance" if per else "shared", bytes_per_instance=ctl.nbytes / Bsz,
+               device=out["device"], rounds=a.rounds)
+    ctl.close()
+    s.close()
+    key = f"C{a.config}" if a.bsz is None else f"C{a.config}x{a.bsz}"
+    path = a.out or os.path.join(ROOT, "profiles", "controller_rollout.json")
+    allr = json.load(open(path)) if os.path.exists(path) else {"tool": "controller_time --rollout"}
+    allr[key] = res
+    print(json.dumps({key: res}))
     with open(path, "w") as f:
         f.write(json.dumps(allr, indent=1) + "\n")
 
