@@ -428,6 +428,8 @@ static int make_plan(const lqmpc_options &o, const Call &c, int device, Plan &pl
     // launches from about 8 192 instances: 0.26 against 0.31 ms at 16 384, 0.25 against 0.19 ms at 4 096).
     // Measured again with the cheaper probe and scatter (C3, T = 30, order on against off): 0.176 against 0.150 ms at 4 096, 0.191 against
     // 0.179 ms at 8 192, 0.195 against 0.215 ms at 16 384.  The crossing still lies between 8 192 and 16 384; the threshold stays.
+    // And with no records staged under the roll key: 0.177 against 0.150 ms at 4 096, 0.190 against 0.180 ms at 8 192, 0.192 against
+    // 0.217 ms at 16 384 (profiles/order_split_speed.json): the same.
     const bool rollout = c.mode == lqmpc::MODE_ROLLOUT || c.mode == lqmpc::MODE_SWEEP;
     const bool packed_size = c.T >= 4 && c.Bsz >= 1024;
     if (pl.rows()) pl.order = rollout && (o.order < 0 ? (c.T >= 4 && c.Bsz >= 8192) : o.order == 1);
@@ -456,13 +458,14 @@ static int ensure_ws(lqmpc_handle *h, const Call &c, const Plan &pl)
     return ensure(h, h->ws, (size_t)lqmpc::generic_ws_entries(c.nx, c.nu, c.N) * (size_t)pl.ws_cols * sizeof(double));
 }
 
-// key, permutation, counters (in front of the hand-back list) and staged records of a difficulty order over B instances
-static int ensure_order(lqmpc_handle *h, int nx, int nu, size_t B)
+// key, permutation, counters (in front of the hand-back list) and, where the call stages them (`records`: build_order), the
+// instance-major records of a difficulty order over B instances
+static int ensure_order(lqmpc_handle *h, int nx, int nu, size_t B, bool records)
 {
     int rc = ensure(h, h->key, B * sizeof(double));
     if (!rc) rc = ensure(h, h->perm, B * sizeof(int));
     if (!rc) rc = ensure_fail(h, (B + FAIL_HDR) * sizeof(int));
-    if (!rc) rc = ensure(h, h->rec, B * (size_t)(nx * nx + nx * nu + nx) * sizeof(double));
+    if (!rc && records) rc = ensure(h, h->rec, B * (size_t)(nx * nx + nx * nu + nx) * sizeof(double));
     return rc;
 }
 
@@ -560,7 +563,15 @@ static int prepare(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, KPa
 static int build_order(lqmpc_handle *h, const Plan &pl, KParams &p)
 {
     if (p.Bsz > (long long)INT32_MAX) return fail(LQMPC_ERR_BAD_ARG, "ordering supports up to 2^31-1 instances");
-    int rc = ensure_order(h, p.nx, p.nu, (size_t)p.Bsz);
+    // No staged records under the roll key for the 16-lane-row kernels with four instances a wavefront (n <= 32): the probe then reads
+    // x0 alone and the sorted walk reads the instance-minor arrays through the permutation.  Measured at C3 x 65 536: staging costs
+    // the probe 7 us (19.6 against 12.5 us; 17.2 us from workgroups of their own in the same launch) and saves the rollout kernel
+    // 1 - 3 us (profiles/order_split_c3_summary.txt).  Everything else stages as before, by policy more than by measurement: the
+    // free-response key's probe holds A and B anyway; a kernel that gives an instance a whole wavefront or a single lane fetches a
+    // contiguous record in fewer lines, but the C4 difference seen (4.131 against 4.138 ms) is inside the run-to-run spread; and the
+    // fused sweep rests on one pair (0.827 ms with records, 0.835 ms without).  None of the three was shown to gain without records.
+    const bool records = !(p.order_roll && p.mode == lqmpc::MODE_ROLLOUT && pl.rows() && p.n <= 32);
+    int rc = ensure_order(h, p.nx, p.nu, (size_t)p.Bsz, records);
     if (rc) return rc;
     // The hand-back count and the order's counters.  First call (or a new buffer): one fill of everything.  After that the probe
     // launch itself zeroes the count and the set of counters the NEXT call will use (the sets alternate), so a call costs no fill
@@ -578,7 +589,7 @@ static int build_order(lqmpc_handle *h, const Plan &pl, KParams &p)
     q.hist = (int *)h->fail.p + 16 + (size_t)h->hist_turn * HIST_INTS;
     q.hist_next = (int *)h->fail.p + 16 + (size_t)(h->hist_turn ^ 1) * HIST_INTS;
     q.fail_count = (int *)h->fail.p;
-    q.stage = (double *)h->rec.p;
+    q.stage = records ? (double *)h->rec.p : nullptr;
     const char *name = nullptr;
     if (pl.family == FAM_JIT) {
         std::string why;
@@ -589,7 +600,7 @@ static int build_order(lqmpc_handle *h, const Plan &pl, KParams &p)
     h->hist_turn ^= 1;
     h->hist_ready = true;
     p.perm = (const int *)h->perm.p;
-    p.rec = (const double *)h->rec.p;
+    p.rec = records ? (const double *)h->rec.p : nullptr;
     return 0;
 }
 
@@ -741,7 +752,7 @@ int lqmpc_reserve(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T)
     Plan pl;
     rc = make_plan(h->opt, c, h->device, pl);
     if (!rc && (pl.rows() || pl.family == FAM_SPEC_TIERED)) rc = ensure_fail(h, ((size_t)Bsz + FAIL_HDR) * sizeof(int));
-    if (!rc && pl.order) rc = ensure_order(h, nx, nu, (size_t)Bsz);
+    if (!rc && pl.order) rc = ensure_order(h, nx, nu, (size_t)Bsz, true);
     if (!rc && pl.ws_cols) rc = ensure_ws(h, c, pl);
     return rc;
 }

@@ -1,5 +1,6 @@
 // lqmpc_probe.h -- the difficulty probe of the ordered rollouts (options.order): one launch computes a key per instance, reserves
-// its position inside its difficulty bucket and stages the instance-major [A | B | x0] records the sorted walk reads.
+// its position inside its difficulty bucket and, under the free-response key, stages the instance-major [A | B | x0] records the
+// sorted walk reads.
 // Device code only (no standard-library header): included by lqmpc_spec.hip for the prebuilt shapes and compiled at run time for the
 // others (lqmpc_jit.hip).
 #pragma once
@@ -14,8 +15,13 @@ namespace lqmpc {
 // It needs neither condensing nor a factorisation (240 FMAs per instance at C3) and orders the batch
 // almost as well as the exact overshoot of the unconstrained minimiser (20.5 % vs 19.8 % of wave-steps
 // left with a constrained instance on C3; natural order 48.7 %).  A heuristic: it only decides which
-// instances share a wavefront, never a result.  The same pass stages the instance-major [A | B | x0]
-// records the sorted walk reads.
+// instances share a wavefront, never a result.
+//
+// Where the host asks for them (p.stage set: build_order) the same pass stages the instance-major [A | B | x0] records the sorted
+// walk reads.  Under the free-response key it has A and B in registers anyway.  The roll key reads nothing of an instance but x0, so
+// with p.stage null under it the launch is the key's chain of dependent latencies alone -- the x0 load, the roll, one LDS and one
+// global round of atomics, the store: no A, no B -- and the sorted walk reads the instance-minor arrays through its permutation
+// (what that saves, and what staging from workgroups of their own in the same launch measured: DESIGN.md section 4.3b).
 //
 // The records of a workgroup's instances are one contiguous piece of p.stage.  Where it fits in LDS (PROBE_WG records: C3's 56 KB)
 // the workgroup lays the piece out there and copies it out 16 bytes a lane, whole 64-byte lines a wavefront -- a lane storing its own
@@ -52,14 +58,17 @@ __device__ __forceinline__ void probe_body(const KParams &p)
 #pragma unroll
     for (int k = 0; k < ORDER_BUCKETS / PROBE_WG; ++k) cnt[tid + k * PROBE_WG] = 0;
     const double *sh = p.sh;
-    double A[NX][NX], Bm[NX][NU], x[NX];
+    double A[NX][NX] = {}, Bm[NX][NU] = {}, x[NX];
 #pragma unroll
-    for (int i = 0; i < NX; ++i) {
+    for (int i = 0; i < NX; ++i) x[i] = p.x0[(long long)i * Bsz + b];
+    if (!p.order_roll || p.stage) {                     // (uniform) the roll key needs x0 only: A and B only to stage them
 #pragma unroll
-        for (int j = 0; j < NX; ++j) A[i][j] = p.A[(long long)(i * NX + j) * Bsz + b];
+        for (int i = 0; i < NX; ++i) {
 #pragma unroll
-        for (int k = 0; k < NU; ++k) Bm[i][k] = p.B[(long long)(i * NU + k) * Bsz + b];
-        x[i] = p.x0[(long long)i * Bsz + b];
+            for (int j = 0; j < NX; ++j) A[i][j] = p.A[(long long)(i * NX + j) * Bsz + b];
+#pragma unroll
+            for (int k = 0; k < NU; ++k) Bm[i][k] = p.B[(long long)(i * NU + k) * Bsz + b];
+        }
     }
     if constexpr (DENSE) {
         if (p.stage) {
