@@ -85,8 +85,10 @@ enum lqmpc_error {
 
 /* Which kernel family runs the batch. */
 enum lqmpc_kernel {
-    LQMPC_KERNEL_AUTO = 0,        /* register-resident specialisation when built for (nx,nu,N); else the workgroup
-                                     kernel when it applies; else generic */
+    LQMPC_KERNEL_AUTO = 0,        /* register-resident specialisation when built for (nx,nu,N); else the 16-lane-row kernel
+                                     compiled at run time where options.jit allows it (nx <= 8, nu <= 4, N*nu <= 48; with
+                                     jit = 2 also 9 <= nx <= 16, nu <= 4, N*nu <= 32); else the workgroup kernel when it
+                                     applies; else generic */
     LQMPC_KERNEL_GENERIC = 1,     /* any dims up to the limits; one instance per lane, workspace in HBM */
     LQMPC_KERNEL_SPECIALIZED = 2, /* fail with LQMPC_ERR_UNSUPPORTED if no specialisation exists */
     LQMPC_KERNEL_WORKGROUP = 3    /* one instance per 256-thread workgroup, matrices in LDS (32 < N*nu <= 128, nx <= 16,
@@ -134,7 +136,10 @@ typedef struct lqmpc_options {
                           the two-tier launch; -1 auto (min(Bsz/8, 4096)), 0 none.  (default -1) */
     int32_t jit;        /* shapes (nx, nu, N) without a prebuilt instantiation: compile the 16-lane-row kernel for them at run time
                           (hiprtc; nx <= 8, nu <= 4, N*nu <= 48; about two seconds per shape and entry point on first use, then
-                          cached) instead of falling back to the generic kernel.  -1 auto (= on), 0 off, 1 on.  (default -1) */
+                          cached) instead of falling back to the generic kernel.  -1 auto (= on), 0 off, 1 on, 2 as 1 and also
+                          the wide-state shapes 9 <= nx <= 16, nu <= 4, N*nu <= 32 (a 12-state or 16-state model with a short
+                          horizon: otherwise on the generic kernel; 10 - 50 s of compile per shape on first use).  Opt-in: the default
+                          routing of those shapes is unchanged.  (default -1) */
     int32_t ctl_wg;     /* prepared controllers (lqmpc_controller_*) on the workgroup kernel's shapes: 0 every step is
                           lqmpc_solve_batch_dev (pass-through), 1 a controller created while this is set keeps one record per
                           instance there as well (kernel AUTO or WORKGROUP, presolve and warm start not switched off).  Opt-in
@@ -166,7 +171,7 @@ int lqmpc_get_options(const lqmpc_handle *h, lqmpc_options *opt);
 /* Run-time compiled kernels (options.jit).  lqmpc_jit_cache_dir: directory where code objects are kept across processes (NULL or
  * "" = in memory only; process-wide).  lqmpc_jit_compile: compile (or find in that directory) every kernel of one shape now -- it needs
  * no GPU, so a build machine can fill the cache; returns the number of code objects available (5) or a negative lqmpc_error, with the
- * compiler's message in `log` if given. */
+ * compiler's message in `log` if given.  It serves the whole domain of options.jit = 2, the wide-state shapes included. */
 int lqmpc_jit_cache_dir(const char *dir);
 int lqmpc_jit_compile(int nx, int nu, int N, char *log, int log_len);
 /* ... and the two on-chip kernels of lqmpc_bounds_batch for a shape (returns 2). */
@@ -291,6 +296,8 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
  * record is [A | B | G | v_r] and then W and P as the block images the kernel works on, a step is one launch of
  * lqmpc_wg_ctl_step_kernel, and W and P are read only by the instances that have to iterate.  Everywhere else the controller keeps
  * device copies of A and B and every step is lqmpc_solve_batch_dev on them, so the interface covers the library's whole domain.
+ * The record kernels stop at nx <= 8: a controller created under options.jit = 2 on a wide-state shape (9 <= nx <= 16) is such a
+ * pass-through, and its steps and rollouts run the run-time compiled 16-lane-row kernel of the shape instead of the generic one.
  * Destroy every controller BEFORE its handle.  Not thread-safe (as the handle).
  *
  * create: A, B per instance (instance-minor; host for _create, device for _create_dev), Q, R, P, lb, ub, x_ref, u_ref HOST (the

@@ -223,7 +223,7 @@ int lqmpc_set_options(lqmpc_handle *h, const lqmpc_options *opt)
     if (opt->r16_maxit < 0 || opt->r16_maxit > 64) return fail(LQMPC_ERR_BAD_ARG, "r16_maxit must be in [0,64]");
     if (opt->r16_build < -1 || opt->r16_build > 1) return fail(LQMPC_ERR_BAD_ARG, "r16_build must be -1, 0 or 1");
     if (opt->nwide < -1) return fail(LQMPC_ERR_BAD_ARG, "nwide must be -1 (auto) or a count");
-    if (opt->jit < -1 || opt->jit > 1) return fail(LQMPC_ERR_BAD_ARG, "jit must be -1, 0 or 1");
+    if (opt->jit < -1 || opt->jit > 2) return fail(LQMPC_ERR_BAD_ARG, "jit must be -1, 0, 1 or 2");
     if (opt->ctl_wg < 0 || opt->ctl_wg > 1) return fail(LQMPC_ERR_BAD_ARG, "ctl_wg must be 0 or 1");
     h->opt = *opt;
     return 0;
@@ -403,9 +403,9 @@ static int make_plan(const lqmpc_options &o, const Call &c, int device, Plan &pl
     // generic / workgroup kernels, as do the shapes whose compile fails (no hiprtc on the machine: reported by last_error once).
     bool jit = false;
     if (o.kernel == LQMPC_KERNEL_AUTO && o.jit != 0 && !built && presolve && warm_start && c.Bsz <= INT32_MAX &&
-        lqmpc::jit_r16_shape(nx, nu, N, nullptr)) {
+        lqmpc::jit_r16_shape(nx, nu, N, nullptr, o.jit == 2)) {
         std::string why;
-        jit = lqmpc::jit_available(device, nx, nu, N, c.mode, &why);
+        jit = lqmpc::jit_available(device, nx, nu, N, c.mode, &why, o.jit == 2);
         if (!jit) g_err = "run-time compile unavailable, using the generic kernels: " + why;
     }
     const bool wg = !spec && !jit && (o.kernel == LQMPC_KERNEL_AUTO || o.kernel == LQMPC_KERNEL_WORKGROUP) && lqmpc::wg_supported(nx, nu, N);

@@ -9,6 +9,7 @@
 // The compile itself needs no GPU (lqmpc_jit_compile can pre-build code objects on a build machine).
 #include "lqmpc_launch.h"
 #include "lqmpc_bounds_chip.h"     // (host side: the LDS-size arithmetic of BigT is checked against the template below)
+#include "lqmpc_r16_body.h"        // (host side: R16Build, the LDS image of the widest shape of the domain)
 #include "../../include/lqmpc.h"
 
 #include <hip/hiprtc.h>
@@ -31,16 +32,25 @@ namespace lqmpc {
 // ---- which shapes the 16-lane-row algorithm serves (lqmpc_r16_body.h / lqmpc_r16_setup.h) ----
 //   n_x <= 8 and n_u <= 4 (register matrices of the set-up), n = N n_u <= 32 with four instances per wavefront (the smaller side of
 //   an active-set system has <= 16 unknowns: one per lane), 32 < n <= 48 with one instance per wavefront (<= 24 unknowns).
-bool jit_r16_shape(int nx, int nu, int N, int *lpi)
+//   wide (options.jit = 2): also 9 <= n_x <= 16 with n <= 32 -- state matrices of 3 x 3 and 4 x 4 tiles, four instances per
+//   wavefront only (32 < n <= 48 at these n_x stays with the workgroup kernel).
+constexpr int NARROW_MAX_NX = 8;                 // the domain without `wide`, and the prepared controller's record kernels
+bool jit_r16_shape(int nx, int nu, int N, int *lpi, bool wide)
 {
     if (lpi) *lpi = 0;
     if (nx < 1 || nu < 1 || N < 1 || nx > SETUP_MAX_NX || nu > SETUP_MAX_NU) return false;
     const int n = N * nu;
     if (n > 48) return false;
+    if (nx > NARROW_MAX_NX && (!wide || n > 32)) return false;
     if (lpi) *lpi = n <= 32 ? 16 : 64;
     return true;
 }
-static int jit_lanes(int nx, int nu, int N) { int l = 0; jit_r16_shape(nx, nu, N, &l); return l; }
+static int jit_lanes(int nx, int nu, int N) { int l = 0; jit_r16_shape(nx, nu, N, &l, true); return l; }
+// Every wide shape can be launched: the LDS image of a wavefront grows with n_x, n_u and n, and the largest of the domain, (16, 4, 8),
+// is within the 64 KB a workgroup may allocate statically -- one wavefront per SIMD, two per CU.
+static_assert(R16Build<16, 4, 8, 16>::LDS_BYTES <= 64 * 1024 && R16Build<16, 4, 8, 16>::WAVES == 1 && R16Build<16, 4, 8, 16>::OCC == 2 &&
+              R16Build<16, 3, 10, 16>::LDS_BYTES <= R16Build<16, 4, 8, 16>::LDS_BYTES && R16Build<16, 1, 32, 16>::LDS_BYTES <= R16Build<16, 4, 8, 16>::LDS_BYTES,
+              "the widest shape of the domain fits a workgroup's LDS");
 
 // ---- hiprtc through dlopen ----
 struct Rtc {
@@ -121,12 +131,12 @@ static std::string program_text(int nx, int nu, int N, int mode)
     if (mode == MODE_PROBE) {
         snprintf(buf, sizeof buf,
                  "#include \"lqmpc_probe.h\"\nnamespace lqmpc {\nextern \"C\" __global__ void __launch_bounds__(PROBE_WG) lqmpc_jit_kernel(KParams p)\n"
-                 "{ probe_body<%d, %d, %d>(p); }\n}\n", nx, nu, N);
+                 "{ %s<%d, %d, %d>(p); }\n}\n", nx > NARROW_MAX_NX ? "probe_body_wide" : "probe_body", nx, nu, N);
         return buf;
     }
     // registers, waves per SIMD and the packed flag: R16Build, as the prebuilt kernels of lqmpc_r16.hip / lqmpc_ctl.hip
     int lpi = 0;
-    jit_r16_shape(nx, nu, N, &lpi);
+    jit_r16_shape(nx, nu, N, &lpi, true);
     snprintf(buf, sizeof buf,
              "#include \"lqmpc_r16_body.h\"\nnamespace lqmpc {\nusing B = R16Build<%d, %d, %d, %d>;\n"
              "extern \"C\" __global__ void __launch_bounds__(64, (B::WAVES)) lqmpc_jit_kernel(KParams p)\n"
@@ -242,10 +252,14 @@ static const Loaded *get_kernel(int device, int nx, int nu, int N, int mode, std
     return &(g_loaded[lk] = l);
 }
 
-bool jit_available(int device, int nx, int nu, int N, int mode, std::string *why)
+bool jit_available(int device, int nx, int nu, int N, int mode, std::string *why, bool wide)
 {
     std::string err;
-    if (!jit_r16_shape(nx, nu, N, nullptr)) { if (why) *why = "outside the 16-lane-row domain (nx <= 8, nu <= 4, N nu <= 48)"; return false; }
+    if (!jit_r16_shape(nx, nu, N, nullptr, wide)) {
+        if (why) *why = wide ? "outside the 16-lane-row domain (nx <= 8, nu <= 4, N nu <= 48; or nx <= 16, nu <= 4, N nu <= 32)"
+                             : "outside the 16-lane-row domain (nx <= 8, nu <= 4, N nu <= 48; nx <= 16 with N nu <= 32 under jit = 2)";
+        return false;
+    }
     const bool ok = get_kernel(device, nx, nu, N, mode, err) != nullptr;
     if (!ok && why) *why = err;
     return ok;
@@ -275,9 +289,10 @@ bool launch_jit(int device, const KParams &p, hipStream_t stream, const char **n
 }
 
 // the on-chip pair of bound-coefficient kernels (lqmpc_bounds_chip.h) of a shape without prebuilt ones: nx <= 8, nu <= 4, any N nu <= 128
+constexpr int BOUNDS_MAX_NX = 8, BOUNDS_MAX_NU = 4;     // (lqmpc_bounds_chip.h asserts the same: its domain does not follow the solver's set-up)
 bool jit_bounds_shape(int nx, int nu, int N)
 {
-    if (nx < 1 || nu < 1 || N < 1 || nx > SETUP_MAX_NX || nu > SETUP_MAX_NU || N * nu > 128) return false;
+    if (nx < 1 || nu < 1 || N < 1 || nx > BOUNDS_MAX_NX || nu > BOUNDS_MAX_NU || N * nu > 128) return false;
     const int lpi = N * nu <= 32 ? 16 : 64;
     return (long long)(64 / lpi) * bounds_big_inst(nx, nu, N, lpi) * 8 <= 160 * 1024;
 }
@@ -326,7 +341,7 @@ int lqmpc_jit_cache_dir(const char *dir)
 int lqmpc_jit_compile(int nx, int nu, int N, char *log, int log_len)
 {
     if (log && log_len > 0) log[0] = '\0';
-    if (!lqmpc::jit_r16_shape(nx, nu, N, nullptr)) return LQMPC_ERR_UNSUPPORTED;
+    if (!lqmpc::jit_r16_shape(nx, nu, N, nullptr, true)) return LQMPC_ERR_UNSUPPORTED;      // (the wide shapes too: what options.jit = 2 routes here)
     std::lock_guard<std::mutex> lock(lqmpc::g_mu);
     int count = 0;
     for (int mode : {(int)lqmpc::MODE_SOLVE, (int)lqmpc::MODE_ROLLOUT, (int)lqmpc::MODE_MAXVN, (int)lqmpc::MODE_SWEEP, (int)lqmpc::MODE_PROBE}) {

@@ -40,8 +40,9 @@ bool launch_wg(const KParams &p, hipStream_t stream, const char **name);
 bool launch_wg_ctl(const KParams &p, hipStream_t stream, const char **name);
 
 // lqmpc_jit.hip: the 16-lane-row kernel (and the probe) of a shape without a prebuilt instantiation, compiled at run time
-bool jit_r16_shape(int nx, int nu, int N, int *lpi);
-bool jit_available(int device, int nx, int nu, int N, int mode, std::string *why);
+// (wide: also the shapes with 9 <= nx <= 16, N nu <= 32 -- options.jit = 2; the prepared controller's record kernels never ask for them)
+bool jit_r16_shape(int nx, int nu, int N, int *lpi, bool wide = false);
+bool jit_available(int device, int nx, int nu, int N, int mode, std::string *why, bool wide = false);
 bool launch_jit(int device, const KParams &p, hipStream_t stream, const char **name, std::string *why);
 bool launch_jit_bounds(int device, const BoundsParams &p, hipStream_t stream, std::string *why);
 

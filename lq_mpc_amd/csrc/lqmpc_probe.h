@@ -36,6 +36,146 @@ struct ProbeRec {
     static constexpr bool DENSE = PROBE_WG * REC * 8 <= 56 * 1024;      // (+ 2 KB of counters: inside the 64 KB of a static allocation)
 };
 
+// The probe of the wide states (9 <= NX <= 16, run-time compiled only): the same keys and the same bookkeeping as probe_body below, but
+// nothing that is NX x NX is held in registers -- 16 x 16 doubles are a lane's whole register file.  Records are copied element by
+// element (they never fit the LDS piece); the roll key reads plant and gain -- scalar loads of the shared block -- where the step uses
+// them (`zs`: an opaque zero set in every step, so that the loads stay inside the loop); the free-response key reads A four rows at a
+// time (`bz`: an opaque copy of the instance index, so that the 256 addresses are formed in the loop and not held across it).
+template <int NX, int NU, int N>
+__device__ __forceinline__ void probe_body_wide(const KParams &p)
+{
+    constexpr int REC = ProbeRec<NX, NU>::REC;
+    static_assert(NX > 8 && !ProbeRec<NX, NU>::DENSE, "wide records do not fit the LDS piece");
+    __shared__ int cnt[ORDER_BUCKETS];
+    const long long Bsz = p.Bsz;
+    const int tid = threadIdx.x;
+    const long long b0 = (long long)blockIdx.x * PROBE_WG, bt = b0 + tid;
+    const bool live = bt < Bsz;
+    const long long b = live ? bt : Bsz - 1;            // surplus lanes of the last workgroup shadow the last instance and write nothing
+    if (p.hist_next) {
+        const long long total = (long long)gridDim.x * PROBE_WG;
+        for (long long e = bt; e < (long long)ORDER_BUCKETS * ORDER_PAD; e += total) p.hist_next[e] = 0;
+    }
+    if (p.fail_count && bt == 0) { p.fail_count[0] = 0; p.fail_count[1] = 0; }
+#pragma unroll
+    for (int k = 0; k < ORDER_BUCKETS / PROBE_WG; ++k) cnt[tid + k * PROBE_WG] = 0;
+    const double *sh = p.sh;
+    double x[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) x[i] = p.x0[(long long)i * Bsz + b];
+    if (p.stage && live) {
+#pragma unroll 1
+        for (int e = 0; e < NX * NX; ++e) p.stage[b * REC + e] = p.A[(long long)e * Bsz + b];
+#pragma unroll 1
+        for (int e = 0; e < NX * NU; ++e) p.stage[b * REC + NX * NX + e] = p.B[(long long)e * Bsz + b];
+#pragma unroll
+        for (int i = 0; i < NX; ++i) p.stage[b * REC + NX * NX + NX * NU + i] = x[i];
+    }
+    __syncthreads();                                    // the counters are zero
+    int raw;
+    if (p.order_roll) {
+        double hk[NU], nhk[NU], hinv[NU];
+#pragma unroll
+        for (int k = 0; k < NU; ++k) {
+            hk[k] = 0.5 * (sh[p.so.ub + k] - sh[p.so.lb + k]);
+            nhk[k] = -hk[k];
+            hinv[k] = 1.0 / hk[k];
+        }
+        const int Ts = p.T < 31 ? p.T : 31;              // (16 (Ts) + 15 < ORDER_BUCKETS)
+        int last = 0, zs = 0;
+        double marg = 0.0;
+#pragma unroll 1
+        for (int t = 0; t < Ts; ++t) {
+            asm volatile("" : "+s"(zs));
+            double u[NU], m = 0.0;
+#pragma unroll
+            for (int k = 0; k < NU; ++k) {
+                double uk = 0.0;
+#pragma unroll
+                for (int j = 0; j < NX; ++j) uk = __builtin_fma(-sh[p.so.Kg + k * NX + j + zs], x[j], uk);
+                m = fmax(m, fabs(uk) * hinv[k]);
+                u[k] = fmin(fmax(uk, nhk[k]), hk[k]);
+            }
+            const bool over = m > 1.0;
+            last = over ? t + 1 : last;
+            marg = (over || t == 0) ? m : marg;
+            double xn[NX];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) {
+                double acc = 0.0;
+#pragma unroll
+                for (int j = 0; j < NX; ++j) acc = __builtin_fma(sh[p.so.At + i * NX + j + zs], x[j], acc);
+#pragma unroll
+                for (int k = 0; k < NU; ++k) acc = __builtin_fma(sh[p.so.Bt + i * NU + k + zs], u[k], acc);
+                xn[i] = acc;
+            }
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[i] = xn[i];
+            if (__ballot(t - last < 3) == 0ull) break;   // no lane of the wavefront saturated in the last three steps: they have settled
+        }
+        double xs = 0.0;                                 // (a NaN anywhere has reached every component by now: first in the order)
+#pragma unroll
+        for (int i = 0; i < NX; ++i) xs += fabs(x[i]);
+        const double g = last > 0 ? 1.0 - 1.0 / marg : fmin(marg, 0.999);
+        raw = (xs < 1e300 && marg == marg) ? 16 * last + (int)(16.0 * g) : ORDER_BUCKETS - 1;
+    } else {
+        double QB[NX][NU], dinv[NU];        // Q B and 1 / ((B'QB + R)_kk h_k)
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int k = 0; k < NU; ++k) {
+                double t = 0.0;
+#pragma unroll
+                for (int j = 0; j < NX; ++j) t = __builtin_fma(sh[p.so.Q + i * NX + j], p.B[(long long)(j * NU + k) * Bsz + b], t);
+                QB[i][k] = t;
+            }
+#pragma unroll
+        for (int k = 0; k < NU; ++k) {
+            double t = sh[p.so.R + k * NU + k];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) t = __builtin_fma(p.B[(long long)(i * NU + k) * Bsz + b], QB[i][k], t);
+            dinv[k] = 1.0 / (t * 0.5 * (sh[p.so.ub + k] - sh[p.so.lb + k]));
+        }
+        double key = 0.0;
+#pragma unroll 1
+        for (int r = 0; r < N; ++r) {
+            long long bz = b;
+            asm volatile("" : "+v"(bz));
+            double xn[NX];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) {
+                if (i % 4 == 0) asm volatile("" ::: "memory");      // (four rows of loads in flight, not the whole matrix)
+                double t = 0.0;
+#pragma unroll
+                for (int j = 0; j < NX; ++j) t = __builtin_fma(p.A[(long long)(i * NX + j) * Bsz + bz], x[j], t);
+                xn[i] = t;
+            }
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[i] = xn[i];
+#pragma unroll
+            for (int k = 0; k < NU; ++k) {
+                double g = 0.0;
+#pragma unroll
+                for (int i = 0; i < NX; ++i) g = __builtin_fma(QB[i][k], x[i], g);
+                key = fmax(key, fabs(g) * dinv[k]);
+            }
+        }
+        const double kk = (key == key) ? key : 1e300;
+        raw = (int)((unsigned)__double2hiint(kk) >> 16) - ((1023 - 2) << 4);      // (the buckets of probe_body)
+    }
+    const int bucket = raw < 0 ? 0 : (raw > ORDER_BUCKETS - 1 ? ORDER_BUCKETS - 1 : raw);
+    const int rank = live ? atomicAdd(&cnt[bucket], 1) : 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < ORDER_BUCKETS / PROBE_WG; ++k) {
+        const int e = tid + k * PROBE_WG;
+        const int c = cnt[e];
+        if (c) cnt[e] = atomicAdd(&p.hist[e * ORDER_PAD], c);
+    }
+    __syncthreads();
+    if (live) ((int2 *)p.key)[b] = make_int2(bucket, cnt[bucket] + rank);
+}
+
 template <int NX, int NU, int N>
 __device__ __forceinline__ void probe_body(const KParams &p)
 {

@@ -59,8 +59,10 @@ struct R16 {
     static constexpr int CN0 = 3 * NX * NX + NU * NU + NX * NU;  // when built for two waves per SIMD)
     static constexpr int CN1 = (NX > NU ? NX : NU) * (2 * NX + 2 * NU);   // ... or the closed loop's per-lane rows of [A_true B_true | Q | R]
     static constexpr int CN = CN0 > CN1 ? CN0 : CN1;
-    static constexpr int SETUP = n * NX;                                 // the hand-over of G aliases the P / W regions (lqmpc_r16_setup.h)
-    static constexpr int oG = 0;
+    // the hand-over of G aliases the P / W regions (lqmpc_r16_setup.h); the wide states (NX > 8: the set-up is a call that stores W as
+    // well, r16_setup_wide) hand it over in the vectors and the constants region behind them, free until the set-up has returned
+    static constexpr int oG = (NX > 8) ? oR : 0;
+    static constexpr int SETUP = oG + n * NX;
     static constexpr int END = oC + CN + (CN & 1);
     static constexpr int oD = (END > SETUP) ? END : SETUP;        // a dummy slot BEHIND both: predicated LDS stores go there instead of toggling exec
     static constexpr int INST = oD + 2;
@@ -75,7 +77,7 @@ struct R16 {
 // lqmpc_r16_lat.hip and serves small batches.
 template <int NX, int NU, int N, int LPI>
 struct R16Build {
-    static constexpr int OCC = ((LPI == 16 && N * NU > 10) || LPI == 64) ? 2 : 1;
+    static constexpr int OCC = ((LPI == 16 && N * NU > 10) || LPI == 64 || NX > 8) ? 2 : 1;
     // two waves per SIMD only where their LDS fits as well ((2,1,30): 33 KB per wavefront -> one wave, the whole register file)
     static constexpr long long LDS_BYTES = (long long)(64 / LPI) * R16<NX, NU, N, LPI, (OCC == 2)>::INST * 8;
     static constexpr int WAVES = ((OCC == 2 || (N * NU <= 10 && LPI == 16)) && LDS_BYTES * 8 <= 160 * 1024) ? 2 : 1;
@@ -231,7 +233,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
 #ifdef LQMPC_NO_ROLL                         // (dev builds: tools/prof_build.sh)
     constexpr bool ROLL = false;
 #else
-    constexpr bool ROLL = LPI == 16 && N * ((NX + 3) / 4) <= 12 && MODE != MODE_MAXVN && !CTL_F && !CTL_REC;
+    constexpr bool ROLL = LPI == 16 && NX <= 8 && N * ((NX + 3) / 4) <= 12 && MODE != MODE_MAXVN && !CTL_F && !CTL_REC;
 #endif
     unsigned cold32[2] = {0u, 0u};
     bool cold_armed = false;                 // set by the caller of qp() for the QP at x0
@@ -265,7 +267,19 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
             bg = p.perm ? (long long)p.perm[sl] : sl;
             Lg = (ldsd *)lds_raw + gq * C::INST;
         }
-        r16_setup_mfma<NX, NU, N, LPI, PACKED, RB, ROLL>(setup_args(p), bg, Lg, L, C::oW, C::oG, C::oD, G, roll_args(p), cold32[0], cold32[1]);
+        if constexpr (NX > 8) {
+            static_assert(LPI == 16 && C::oG >= 2 * C::PK, "wide states: four instances per wavefront, G handed over behind P and W");
+            r16_setup_wide<NX, NU, N, PACKED, RB>(setup_args(p), bg, Lg, C::oW, C::oG, C::oD);
+#pragma unroll
+            for (int s = 0; s < RB; ++s) {
+#pragma unroll
+                for (int a = 0; a < NX; ++a) {
+                    const double x = L[C::oG + (vrow[s] ? rw[s] * NX + a : 0)];
+                    G[s][a] = vrow[s] ? x : 0.0;
+                }
+            }
+            __syncthreads();
+        } else r16_setup_mfma<NX, NU, N, LPI, PACKED, RB, ROLL>(setup_args(p), bg, Lg, L, C::oW, C::oG, C::oD, G, roll_args(p), cold32[0], cold32[1]);
         if constexpr (!LAZY_P) r16_build_P<NX, NU, N, LPI, PACKED>(setup_args(p), bg, Lg, C::oP, C::oD);
         RPROF(5);
         // constant part of the unconstrained minimiser: v_r = -W (2 gref + P centre) = -2 W gref - centre (references / off-centre boxes only)
@@ -278,44 +292,85 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                 double qr[RB];
 #pragma unroll
                 for (int s = 0; s < RB; ++s) qr[s] = 0.0;
-                double lam[NX], A2[NX][NX], B2[NX][NU];
+                constexpr bool WIDE = NX > 8;
+                double lam[NX], A2[WIDE ? 1 : NX][WIDE ? 1 : NX], B2[WIDE ? 1 : NX][WIDE ? 1 : NU];
+                if constexpr (WIDE) {
+                    // wide states: the model does not fit a lane's registers (16 x 16 + 16 x 4 doubles), so the recursion is spread over
+                    // the lanes of the instance -- lane i < NX owns component i of lam (column i of A and row i of Q_r in 2 NX registers),
+                    // the stage's lam goes round through LDS; a row's own input column of B is fetched by its lane
+                    const int ia = i < NX ? i : 0;
+                    double Ac[NX], Bc[RB][NX];
 #pragma unroll
-                for (int a = 0; a < NX; ++a) {
-                    lam[a] = 0.0;
+                    for (int c = 0; c < NX; ++c) {
+                        lam[c] = 0.0;
+                        Ac[c] = p.rec ? p.rec[b * REC + c * NX + ia] : p.A[(long long)(c * NX + ia) * Bsz + b];
 #pragma unroll
-                    for (int c = 0; c < NX; ++c) A2[a][c] = p.rec ? p.rec[b * REC + a * NX + c] : p.A[(long long)(a * NX + c) * Bsz + b];
-#pragma unroll
-                    for (int k = 0; k < NU; ++k) B2[a][k] = p.rec ? p.rec[b * REC + NX * NX + a * NU + k] : p.B[(long long)(a * NU + k) * Bsz + b];
-                }
-#pragma unroll 1
-                for (int r = N - 1; r >= 0; --r) {
-                    const int oQ = (r < N - 1) ? p.so.Q : p.so.P;
-                    double l2[NX];
-#pragma unroll
-                    for (int a = 0; a < NX; ++a) {
-                        double t = 0.0;
-#pragma unroll
-                        for (int c = 0; c < NX; ++c) t = __builtin_fma(sh[oQ + a * NX + c], -sh[p.so.xref + c * N + r], t);
-#pragma unroll
-                        for (int c = 0; c < NX; ++c) t = __builtin_fma(A2[c][a], lam[c], t);
-                        l2[a] = t;
+                        for (int s = 0; s < RB; ++s)
+                            Bc[s][c] = p.rec ? p.rec[b * REC + NX * NX + c * NU + rw[s] % NU] : p.B[(long long)(c * NU + rw[s] % NU) * Bsz + b];
                     }
-#pragma unroll
-                    for (int a = 0; a < NX; ++a) lam[a] = l2[a];
-#pragma unroll
-                    for (int s = 0; s < RB; ++s) {
-                        const int ui = rw[s] % NU;
+#pragma unroll 1
+                    for (int r = N - 1; r >= 0; --r) {
+                        const int oQ = (r < N - 1) ? p.so.Q : p.so.P;
                         double t = 0.0;
 #pragma unroll
-                        for (int k = 0; k < NU; ++k) {
+                        for (int c = 0; c < NX; ++c) t = __builtin_fma(sh[oQ + ia * NX + c], -sh[p.so.xref + c * N + r], t);
+#pragma unroll
+                        for (int c = 0; c < NX; ++c) t = __builtin_fma(Ac[c], lam[c], t);
+                        yL[i] = t;
+                        __syncthreads();
+#pragma unroll
+                        for (int a = 0; a < NX; ++a) lam[a] = yL[a];
+                        __syncthreads();
+#pragma unroll
+                        for (int s = 0; s < RB; ++s) {
+                            const int ui = rw[s] % NU;
                             double tk = 0.0;
 #pragma unroll
-                            for (int a = 0; a < NX; ++a) tk = __builtin_fma(B2[a][k], lam[a], tk);
+                            for (int a = 0; a < NX; ++a) tk = __builtin_fma(Bc[s][a], lam[a], tk);
 #pragma unroll
-                            for (int j = 0; j < NU; ++j) tk = __builtin_fma(-sh[p.so.R + k * NU + j], sh[p.so.uref + j * N + r], tk);
-                            t = (ui == k) ? tk : t;
+                            for (int j = 0; j < NU; ++j) tk = __builtin_fma(-sh[p.so.R + ui * NU + j], sh[p.so.uref + j * N + r], tk);
+                            qr[s] = (vrow[s] && rw[s] / NU == r) ? 2.0 * tk : qr[s];
                         }
-                        qr[s] = (vrow[s] && rw[s] / NU == r) ? 2.0 * t : qr[s];
+                    }
+                } else {
+#pragma unroll
+                    for (int a = 0; a < NX; ++a) {
+                        lam[a] = 0.0;
+#pragma unroll
+                        for (int c = 0; c < NX; ++c) A2[a][c] = p.rec ? p.rec[b * REC + a * NX + c] : p.A[(long long)(a * NX + c) * Bsz + b];
+#pragma unroll
+                        for (int k = 0; k < NU; ++k) B2[a][k] = p.rec ? p.rec[b * REC + NX * NX + a * NU + k] : p.B[(long long)(a * NU + k) * Bsz + b];
+                    }
+#pragma unroll 1
+                    for (int r = N - 1; r >= 0; --r) {
+                        const int oQ = (r < N - 1) ? p.so.Q : p.so.P;
+                        double l2[NX];
+#pragma unroll
+                        for (int a = 0; a < NX; ++a) {
+                            double t = 0.0;
+#pragma unroll
+                            for (int c = 0; c < NX; ++c) t = __builtin_fma(sh[oQ + a * NX + c], -sh[p.so.xref + c * N + r], t);
+#pragma unroll
+                            for (int c = 0; c < NX; ++c) t = __builtin_fma(A2[c][a], lam[c], t);
+                            l2[a] = t;
+                        }
+#pragma unroll
+                        for (int a = 0; a < NX; ++a) lam[a] = l2[a];
+#pragma unroll
+                        for (int s = 0; s < RB; ++s) {
+                            const int ui = rw[s] % NU;
+                            double t = 0.0;
+#pragma unroll
+                            for (int k = 0; k < NU; ++k) {
+                                double tk = 0.0;
+#pragma unroll
+                                for (int a = 0; a < NX; ++a) tk = __builtin_fma(B2[a][k], lam[a], tk);
+#pragma unroll
+                                for (int j = 0; j < NU; ++j) tk = __builtin_fma(-sh[p.so.R + k * NU + j], sh[p.so.uref + j * N + r], tk);
+                                t = (ui == k) ? tk : t;
+                            }
+                            qr[s] = (vrow[s] && rw[s] / NU == r) ? 2.0 * t : qr[s];
+                        }
                     }
                 }
 #pragma unroll
@@ -419,7 +474,11 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
     ldsd *cQ = L + C::oC, *cR = cQ + NX * NX;
     if constexpr (MODE == MODE_ROLLOUT || CTL_R) {
     } else if constexpr (OCC == 2) {
-        if (i == 0) {
+        if constexpr (NX > 8) {
+            // (wide states: 3 x 256 values -- the copy is spread over the lanes of the instance instead of left to its first lane)
+            for (int e = i; e < NX * NX; e += LPI) cQ[e] = sh[p.so.Q + e];
+            for (int e = i; e < NU * NU; e += LPI) cR[e] = sh[p.so.R + e];
+        } else if (i == 0) {
 #pragma unroll
             for (int a = 0; a < NX; ++a) {
 #pragma unroll
@@ -1028,7 +1087,13 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
         double Am[NX][NX], Bmm[NX][NU], Pm[NX][NX];
         ldsd *cA = cR + NU * NU, *cB = cA + NX * NX, *cP = cB + NX * NU;
         if constexpr (OCC == 2) {
-            if (i == 0) {
+            if constexpr (NX > 8) {
+                for (int e = i; e < NX * NX; e += LPI) {
+                    cA[e] = p.rec ? p.rec[bq * REC + e] : p.A[(long long)e * Bsz + bq];
+                    cP[e] = sh[p.so.P + e];
+                }
+                for (int e = i; e < NX * NU; e += LPI) cB[e] = p.rec ? p.rec[bq * REC + NX * NX + e] : p.B[(long long)e * Bsz + bq];
+            } else if (i == 0) {
 #pragma unroll
                 for (int a = 0; a < NX; ++a) {
 #pragma unroll
@@ -1065,6 +1130,65 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
         auto Bv = [&](int a, int k) -> double { if constexpr (OCC == 2) return cB[a * NU + k]; else return Bmm[a][k]; };
         auto Pv = [&](int a, int c) -> double { if constexpr (OCC == 2) return cP[a * NX + c]; else return Pm[a][c]; };
         auto value_fn = [&](const double (&x0v)[NX], const double (&v)[RB]) -> double {
+            if constexpr (NX > 8) {
+                // wide states: the roll spread over the lanes of the instance like the closed loop below -- lane a < NX owns row a of
+                // [A B] and of the stage weight (read from the constants in LDS, 3 NX + NU values a stage instead of 3 NX^2), the new state
+                // goes round by row broadcasts, lane k < NU owns row k of R; the partial costs are summed over the lanes at the end.
+                // (`zc`: an opaque zero set in every stage, so that the rows are read where they are used and not held across qp().)
+                static_assert(OCC == 2 && LPI == 16, "wide states: constants in LDS, four instances per wavefront");
+                const int ia = i < NX ? i : 0, ik = i < NU ? i : 0;
+                double xs[NX], cx, cu = 0.0;
+#pragma unroll
+                for (int a = 0; a < NX; ++a) xs[a] = x0v[a];
+                {
+                    double xm = xs[0], qx = 0.0;
+#pragma unroll
+                    for (int a = 1; a < NX; ++a) xm = (i == a) ? xs[a] : xm;
+#pragma unroll
+                    for (int cc = 0; cc < NX; ++cc) qx = __builtin_fma(cQ[ia * NX + cc], xs[cc], qx);
+                    cx = xm * qx;
+                }
+#pragma unroll
+                for (int s = 0; s < RB; ++s) xL[rw[s]] = vrow[s] ? fmin(fmax(v[s], -h[s]), h[s]) + ctr[s] : 0.0;
+                __syncthreads();
+                int zc = 0;
+#pragma unroll 1
+                for (int st = 0; st < N; ++st) {
+                    asm volatile("" : "+v"(zc));
+                    const ldsd *rA = cA + ia * NX + zc, *rB = cB + ia * NU + zc, *rW = ((st == N - 1) ? cP : cQ) + ia * NX + zc, *rR = cR + ik * NU + zc;
+                    double u[NU], xm = 0.0, qx = 0.0, ru = 0.0;
+#pragma unroll
+                    for (int k = 0; k < NU; ++k) u[k] = xL[st * NU + k];
+#pragma unroll
+                    for (int cc = 0; cc < NX; ++cc) xm = __builtin_fma(rA[cc], xs[cc], xm);
+#pragma unroll
+                    for (int k = 0; k < NU; ++k) xm = __builtin_fma(rB[k], u[k], xm);
+#pragma unroll
+                    for (int a = 0; a < NX; ++a) xs[a] = ibcast<LPI>(xm, a);
+                    double dm = xm;
+                    if (p.has_ref) dm -= sh[p.so.xref + ia * N + st];
+#pragma unroll
+                    for (int cc = 0; cc < NX; ++cc) qx = __builtin_fma(rW[cc], p.has_ref ? xs[cc] - sh[p.so.xref + cc * N + st] : xs[cc], qx);
+                    cx = __builtin_fma(dm, qx, cx);
+                    if (p.has_ref) {
+#pragma unroll
+                        for (int k = 0; k < NU; ++k) u[k] -= sh[p.so.uref + k * N + st];
+                    }
+                    double um = u[0];
+#pragma unroll
+                    for (int k = 1; k < NU; ++k) um = (i == k) ? u[k] : um;
+#pragma unroll
+                    for (int j = 0; j < NU; ++j) ru = __builtin_fma(rR[j], u[j], ru);
+                    cu = __builtin_fma(um, ru, cu);
+                }
+                __syncthreads();
+                double c = 0.0;
+#pragma unroll
+                for (int a = 0; a < NX; ++a) c += ibcast<LPI>(cx, a);
+#pragma unroll
+                for (int k = 0; k < NU; ++k) c += ibcast<LPI>(cu, k);
+                return c;
+            }
             double xs[NX], c = 0.0;
 #pragma unroll
             for (int a = 0; a < NX; ++a) xs[a] = x0v[a];

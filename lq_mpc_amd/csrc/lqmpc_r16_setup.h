@@ -21,7 +21,8 @@
 //     W = (2H)^-1 = 1/2 T D^-1 T' = sum_M T(:, M) (D_M^-1 / 2) T(:, M)'       (one update per column tile M of 4 / NU stages, on 4x4 tiles),
 //     G rows of stage k = -K_k Acl_{k-1} .. Acl_0 = -rho_k(-1)                    (what the rows rho_k have become after stage 0),
 // and the rows rho_k advance inside the same backward sweep (rho_k(j-1) = rho_k(j) Acl_j), so nothing is stored per stage.
-// Sizes: state matrices of up to 8 x 8 are 2 x 2 tiles (TX = 2: every product of the recursion becomes TX^2..TX^3 tile products);
+// Sizes: state matrices of up to 8 x 8 are 2 x 2 tiles (TX = 2: every product of the recursion becomes TX^2..TX^3 tile products),
+// the wide states of up to 16 x 16 are 3 x 3 or 4 x 4 tiles (run-time compiled only, as a call: r16_setup_wide at the end of this file);
 // stage blocks of 1, 2 or 4 inputs tile the rows exactly, 3 inputs are padded to 4 with a dummy input (zero column of B, unit
 // weight: decoupled, its rows are never stored).  The inverse of Re for 4 inputs goes by 2 x 2 blocks (Schur complement), again
 // with products and element-wise reciprocals only.
@@ -33,14 +34,14 @@
 
 namespace lqmpc {
 
-constexpr int SETUP_MAX_NX = 8, SETUP_MAX_NU = 4;   // what this set-up serves (the run-time compile asks: lqmpc_jit.hip)
+constexpr int SETUP_MAX_NX = 16, SETUP_MAX_NU = 4;  // what this set-up serves (the run-time compile asks: lqmpc_jit.hip)
 
 // (a)' b + c on register matrices (four independent blocks per wavefront)
 __device__ __forceinline__ double mm4(double a, double b, double c = 0.0) { return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0); }
 
 template <int NX, int NU, int N, int LPI>
 struct SetupT {
-    static_assert(NX >= 1 && NX <= SETUP_MAX_NX, "state matrices are at most 2 x 2 tiles of 4 x 4");
+    static_assert(NX >= 1 && NX <= SETUP_MAX_NX, "state matrices are at most 4 x 4 tiles of 4 x 4");
     static_assert(NU >= 1 && NU <= SETUP_MAX_NU, "stage blocks of 1..4 rows");
     static constexpr int TX = (NX + 3) / 4;                   // tiles per side of a state matrix
     static constexpr int NUP = (NU == 3) ? 4 : NU;            // rows of a stage block in the tiled (padded) row space
@@ -311,11 +312,14 @@ __device__ __attribute__((noinline)) void r16_build_P(const SetupArgs p, long lo
 // and a clip for the four instances at once.  Zero references and a centred box only: otherwise -K_j x_j is not the
 // unconstrained input (ra.roll).  coldL / coldU: bit (j NU + k) per clipped pair, in the lanes of the instance (q = lane / 16) as everywhere
 // outside the set-up; both zero: no guess.
-template <int NX, int NU, int N, int LPI, bool PACKED, int RB, bool ROLL = false>
+//
+// READ_G = false (the wide states, r16_setup_wide below): G stays in LDS at oG, which then must not alias W; the caller reads it back.
+template <int NX, int NU, int N, int LPI, bool PACKED, int RB, bool ROLL = false, bool READ_G = true>
 __device__ __forceinline__ void r16_setup_mfma(const SetupArgs &p, long long bg, wg::ldsd *Lg, wg::ldsd *Lq, int oW, int oG, int oD,
                                               double (&G)[RB][NX], const RollArgs &ra, unsigned &coldL, unsigned &coldU)
 {
     static_assert(!ROLL || (LPI == 16 && N * NU <= 32), "the cold-start roll serves the four-instance mapping");
+    static_assert(READ_G || !ROLL, "the roll runs under the read-back of G");
     using T = SetupT<NX, NU, N, LPI>;
     constexpr int n = T::n, NT = T::NT, SPT = T::SPT, NTM = T::NTM, TX = T::TX, NUP = T::NUP;
     const int lane = threadIdx.x, r = lane >> 4, c = lane & 3, g = (lane >> 2) & 3;
@@ -520,8 +524,8 @@ __device__ __forceinline__ void r16_setup_mfma(const SetupArgs &p, long long bg,
 #pragma unroll
         for (int a = 0; a < TX; ++a) Gs[(4 * a + r < NX && row >= 0) ? row * NX + 4 * a + r : dG] = -rho[m][a];
     }
-    __syncthreads();
-    {
+    if constexpr (READ_G) {
+        __syncthreads();
         const int i = lane % LPI;
         const wg::ldsd *Gq = Lq + oG;
 #pragma unroll
@@ -533,8 +537,8 @@ __device__ __forceinline__ void r16_setup_mfma(const SetupArgs &p, long long bg,
                 G[s][a] = row < n ? x : 0.0;
             }
         }
+        __syncthreads();
     }
-    __syncthreads();
 
     // ---- the cold-start guess: saturated roll-forward from x0 (column 0 of a register matrix per row tile) ----
     // (here, in one block with the stores of W: its dependent chain of products runs under their address arithmetic and LDS issue)
@@ -622,6 +626,20 @@ __device__ __forceinline__ void r16_setup_mfma(const SetupArgs &p, long long bg,
                 }
     }
     __syncthreads();
+}
+
+// The set-up of the wide states (9 <= NX <= 16: state matrices of 3 x 3 or 4 x 4 tiles), four instances per wavefront: the same sweep
+// as a function of its own.  Its live set (A, Q, S and the products of a stage: 6 x 16 register matrices at TX = 4; rho and Wacc on
+// top) takes most of the 512 registers of a wavefront; inlined, the allocator carries that pressure into the loops of the solver
+// behind it (scratch reloads in the closed-loop step).  As a call -- like r16_build_P -- it costs its frame once per instance, and
+// the solver is allocated as if the set-up were not there.  G is left in LDS at oG (outside W and P: R16<>::oG), W at oW; ends with
+// a barrier.  No cold-start roll (a warm-start guess: it never decides the answer; KT would be N x TX registers more).
+template <int NX, int NU, int N, bool PACKED, int RB>
+__device__ __attribute__((noinline)) void r16_setup_wide(const SetupArgs p, long long bg, wg::ldsd *Lg, int oW, int oG, int oD)
+{
+    double G[RB][NX];
+    unsigned cl, cu;
+    r16_setup_mfma<NX, NU, N, 16, PACKED, RB, false, false>(p, bg, Lg, Lg, oW, oG, oD, G, RollArgs{nullptr, 0, 0, 0}, cl, cu);
 }
 
 }  // namespace lqmpc
