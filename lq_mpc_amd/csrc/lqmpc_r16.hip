@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(64, (R16Build<NX, NU, N, LPI>::WAVES)) lqmpc_r
 {
     using C = R16<NX, NU, N, LPI, (R16Build<NX, NU, N, LPI>::OCC == 2)>;
     __shared__ double lds_raw[C::IPW * C::INST];
-    r16_body<NX, NU, N, MODE, LPI, R16Build<NX, NU, N, LPI>::OCC>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
+    r16_body<NX, NU, N, MODE, LPI, R16Build<NX, NU, N, LPI>::OCC, (MODE == MODE_ROLLOUT && R16Build<NX, NU, N, LPI>::CHUNKS)>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
 }
 
 template <int NX, int NU, int N, int LPI>
@@ -45,7 +45,7 @@ static void launch_r16_one(const KParams &p, hipStream_t stream)
     else if (p.mode == MODE_SWEEP) hipLaunchKernelGGL((lqmpc_r16_kernel<NX, NU, N, MODE_SWEEP, LPI>), grid, dim3(64), 0, stream, p);
     else {
 #ifdef LQMPC_R16_PROF
-        long long z[32] = {0};
+        long long z[36] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_r16_prof), z, sizeof z);
 #endif
         hipLaunchKernelGGL((lqmpc_r16_kernel<NX, NU, N, MODE_ROLLOUT, LPI>), grid, dim3(64), 0, stream, p);
@@ -61,6 +61,8 @@ static void launch_r16_one(const KParams &p, hipStream_t stream)
                 (double)z[25] / (z[16] ? z[16] : 1));
         fprintf(stderr, "r16 prof (grid): step 0: %.0f ticks/wave, %.2f wave-iterations/wave, %.2f of them general; %lld of %lld wavefronts ever took the general (P-reading) path\n",
                 (double)z[27] / z[15], (double)z[28] / z[15], (double)z[29] / z[15], z[30], z[15]);
+        fprintf(stderr, "r16 prof (grid): chunks of iteration-free steps: %lld committed, %lld discarded with %lld steps computed for nothing (%.2f %% of the free wave-steps)\n",
+                z[31], z[32], z[33], 100.0 * (double)z[33] / (z[10] ? z[10] : 1));
 #endif
     }
 }

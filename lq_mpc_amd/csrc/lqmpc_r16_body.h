@@ -23,11 +23,14 @@ using wg::fmac_rowb_lanes4x2;
 using wg::dpp_settle;
 
 #ifdef LQMPC_R16_PROF
-__device__ long long g_r16_prof[32];
+__device__ long long g_r16_prof[36];
 #define RPROF(k) do { const long long now_ = clock64(); if (threadIdx.x == 0 && blockIdx.x == PROFBLK) g_r16_prof[k] += now_ - prof_t; if (k < 7) prof_ph[k] += now_ - prof_t; prof_t = clock64(); } while (0)
 #define RPROF_START long long prof_t = clock64()
 // whole-grid accounting (every wavefront adds): [8] cycles of iteration-free wave-steps, [9] cycles of wave-steps with active-set
-// iterations, [10] / [11] their numbers, [12] wave-iterations, [13] set-up cycles, [14] total cycles, [15] wavefronts
+// iterations, [10] / [11] their numbers, [12] wave-iterations, [13] set-up cycles, [14] total cycles, [15] wavefronts; [31] chunks of
+// iteration-free steps committed (their steps count in [10]), [32] chunks discarded, [33] steps computed in discarded chunks.
+// A pass of the closed loop is credited to [8]..[12] at the top of the NEXT pass, so the last pass of every wavefront is in none of them:
+// one step, or all the steps of a last committed chunk (up to FREE_KMAX; 5 at T = 30).  [31]..[33] count every chunk.
 #define RPROF_ADD(k, v) do { if (threadIdx.x == 0) atomicAdd((unsigned long long *)&g_r16_prof[k], (unsigned long long)(v)); } while (0)
 #ifndef PROFBLK
 #define PROFBLK 0
@@ -81,6 +84,9 @@ struct R16Build {
     // two waves per SIMD only where their LDS fits as well ((2,1,30): 33 KB per wavefront -> one wave, the whole register file)
     static constexpr long long LDS_BYTES = (long long)(64 / LPI) * R16<NX, NU, N, LPI, (OCC == 2)>::INST * 8;
     static constexpr int WAVES = ((OCC == 2 || (N * NU <= 10 && LPI == 16)) && LDS_BYTES * 8 <= 160 * 1024) ? 2 : 1;
+    // iteration-free closed-loop steps in speculative chunks: the rollout kernels of the throughput build in which they were measured
+    // as a gain -- C3 (four instances per wavefront) and C4 (one) -- and no other
+    static constexpr bool CHUNKS = NX == 4 && NU == 2 && ((LPI == 16 && N == 10) || (LPI == 64 && N == 20));
 };
 
 // ---- the per-instance primitives in the two mappings ----
@@ -161,7 +167,8 @@ __device__ __forceinline__ unsigned row_umax(unsigned x)
 // OCC = 2: built for two waves per SIMD (256 registers): the horizon loops of the condensing stay rolled and the stage weights
 // and the plant live in LDS instead of registers (they are the loop-invariant values the allocator would otherwise reload
 // from scratch in every step).
-template <int NX, int NU, int N, int MODE, int LPI = 16, int OCC = 1>
+// CHUNKS: the closed loop takes its iteration-free steps in speculative chunks (below, "Iteration-free steps in speculative chunks").
+template <int NX, int NU, int N, int MODE, int LPI = 16, int OCC = 1, bool CHUNKS = false>
 __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long long slot0, long long slot_end)
 {
     constexpr bool PACKED = (OCC == 2);
@@ -1361,18 +1368,83 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
         }
 #ifdef LQMPC_R16_PROF
         long long prof_ts = 0, prof_acc[5] = {0, 0, 0, 0, 0};
+        int prof_nst = 1;                    // steps the previous pass of the loop below covered (a committed chunk: all of its steps)
 #endif
+        // Iteration-free steps in speculative chunks.  Once a step of the wavefront was inside the box for all its instances, the next
+        // FREE_KMAX steps are taken without a branch on a vector result: G x + v_r, the outside test of every row slot OR-ed into one
+        // scalar mask, the input WITHOUT the clip, the plant and the cost -- the FMAs of the single step below in the same order.  The
+        // mask is tested once behind the chunk.  Zero: every row was inside at every step, so the clip was the identity and the chunk is
+        // the steps bit for bit.  Otherwise (a NaN counts as outside) the state and the costs are put back and step t goes through the
+        // single step; no new chunk before a step of the wavefront has gone through qp() -- the step outside lies within FREE_KMAX steps
+        // and every chunk before it would be discarded.  Not with a trajectory requested: its stores would need the steps one by one.
+        // CHUNKS: only the kernels in which the chunks were measured as a gain have them (R16Build::CHUNKS); everywhere
+        // else the block below is dead code and the kernel compiles to what it was without it.
+        constexpr int FREE_KMAX = 8;
+        const bool free_chunks = CHUNKS && !p.X && !p.U;
+        bool prev_free = false, chunk_hold = false;          // wave-uniform
+        mask_t rows_mask[RB];                                // the lanes of the wavefront that hold a row in slot s
+#pragma unroll
+        for (int s = 0; s < RB; ++s) rows_mask[s] = __ballot(vrow[s]);
         for (int t = 0; t < p.T; ++t) {
             double v[RB], u[NU], xn[NX];
 #ifdef LQMPC_R16_PROF
             if (t == 1) { RPROF_ADD(27, clock64() - prof_ts); RPROF_ADD(28, prof_wit); RPROF_ADD(29, prof_slow); }
             if (t > 0) {
                 const long long d_ = clock64() - prof_ts;
-                if (prof_wit) { prof_acc[1] += d_; prof_acc[3] += 1; prof_acc[4] += prof_wit; } else { prof_acc[0] += d_; prof_acc[2] += 1; }
+                if (prof_wit) { prof_acc[1] += d_; prof_acc[3] += 1; prof_acc[4] += prof_wit; } else { prof_acc[0] += d_; prof_acc[2] += prof_nst; }
             }
             prof_ts = clock64();
             prof_wit = 0;
+            prof_nst = 1;
 #endif
+            if (free_chunks && prev_free && !chunk_hold && p.T - t >= 2) {
+                const int kc = p.T - t < FREE_KMAX ? p.T - t : FREE_KMAX;
+                double x_keep[NX];
+                const double costx_keep = costx, costu_keep = costu;
+#pragma unroll
+                for (int a = 0; a < NX; ++a) x_keep[a] = x[a];
+                mask_t outside = 0;
+#pragma unroll 1
+                for (int j = 0; j < kc; ++j) {
+#pragma unroll
+                    for (int s = 0; s < RB; ++s) {
+                        double acc = vr[s];
+#pragma unroll
+                        for (int a = 0; a < NX; ++a) acc = __builtin_fma(G[s][a], x[a], acc);
+                        v[s] = acc;
+                        outside |= __ballot(!(fabs(acc) <= h[s])) & rows_mask[s];     // (the compare's own mask, no bool in between)
+                    }
+                    const double um = v[0] + ctr[0];
+#pragma unroll
+                    for (int k = 0; k < NU; ++k) u[k] = ibcast<LPI>(um, k);
+                    double xm = 0.0, qx = 0.0, ru = 0.0;
+#pragma unroll
+                    for (int c = 0; c < NX; ++c) xm = __builtin_fma(Ar(c), x[c], xm);
+#pragma unroll
+                    for (int k = 0; k < NU; ++k) xm = __builtin_fma(Br(k), u[k], xm);
+#pragma unroll
+                    for (int a = 0; a < NX; ++a) x[a] = ibcast<LPI>(xm, a);
+#pragma unroll
+                    for (int c = 0; c < NX; ++c) qx = __builtin_fma(Qr(c), x[c], qx);
+                    costx = __builtin_fma(xm, qx, costx);
+#pragma unroll
+                    for (int j2 = 0; j2 < NU; ++j2) ru = __builtin_fma(Rr(j2), u[j2], ru);
+                    costu = __builtin_fma(um, ru, costu);
+                }
+                if (outside == 0ull) {
+#ifdef LQMPC_R16_PROF
+                    prof_nst = kc;
+                    RPROF_ADD(31, 1);
+#endif
+                    t += kc - 1;                             // (pL = pU = 0 already: the step before was inside)
+                    continue;
+                }
+                RPROF_ADD(32, 1); RPROF_ADD(33, kc);
+#pragma unroll
+                for (int a = 0; a < NX; ++a) x[a] = x_keep[a];
+                costx = costx_keep; costu = costu_keep;
+                chunk_hold = true;
+            }
             // most steps of most wavefronts: the unconstrained minimiser of every instance of the wavefront is inside its box --
             // one compare per row slot and one wave-wide test, none of the mask bookkeeping of qp()
             bool inside = false;
@@ -1390,7 +1462,8 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
             }
             cold_armed = ROLL && t == 0;
             if (inside) { pL = 0; pU = 0; }
-            else qp(x, v);
+            else { qp(x, v); chunk_hold = false; }
+            prev_free = inside;
             const double um = fmin(fmax(v[0], -h[0]), h[0]) + ctr[0];     // the input of my first row: u_i in lane i < NU
             stage_input(v, 0, u);
             double xm = 0.0, qx = 0.0, ru = 0.0;
