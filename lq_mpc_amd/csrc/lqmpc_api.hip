@@ -1,6 +1,7 @@
 // lqmpc_api.hip -- host side of the C ABI declared in include/lqmpc.h: handle, argument checks,
 // shared-block packing, workspace management, kernel dispatch, host<->device staging.
 #include "lqmpc_launch.h"
+#include "lqmpc_host.h"
 #include "../../include/lqmpc.h"
 
 #include <algorithm>
@@ -52,14 +53,15 @@ struct lqmpc_handle {
     bool hist_ready = false;         // both sets of order counters are zero / being zeroed by the probe launches: no fill needed
     int hist_turn = 0;               // which set the next probe counts into
     DevBuf st2, it2;                 // lqmpc_sweep_batch_dev without a fused kernel: status / iters of the max-V_N pass
-    DevBuf stage[12];                // host-flavour staging (inputs and outputs)
-    DevBuf arena;                    // host-flavour staging of small calls: one packed block, one copy each way
-    HostBuf arena_pin;
+    DevBuf arena;                    // host-flavour staging (Stager): every array of the call in one block
+    HostBuf arena_pin;               // ... its pinned image, for the small calls that go up and come back in one copy each
     HostBuf shared_pin[2];           // source of the shared block's upload
     int shared_turn = 0;
     std::vector<double> shared_host; // last uploaded shared block
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    const char *last_kernel = "none";
+    std::string last_kernel = "none";
+    uint64_t last_owner = 0;         // the id of the controller whose record path set last_kernel; 0: a one-shot call did
+    uint64_t ctl_ids = 0;            // ids given to controllers so far
 };
 
 constexpr int JIT_FALLBACK_COLS = 1024;   // workspace columns of the generic kernel when it only serves a hand-back list
@@ -182,11 +184,7 @@ int lqmpc_destroy(lqmpc_handle *h)
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    if (h->shared.p) (void)hipFree(h->shared.p);
-    if (h->ws.p) (void)hipFree(h->ws.p);
-    for (DevBuf *b : {&h->key, &h->perm, &h->rec, &h->fail, &h->st2, &h->it2}) if (b->p) (void)hipFree(b->p);
-    for (auto &b : h->stage) if (b.p) (void)hipFree(b.p);
-    if (h->arena.p) (void)hipFree(h->arena.p);
+    for (DevBuf *b : {&h->shared, &h->ws, &h->key, &h->perm, &h->rec, &h->fail, &h->st2, &h->it2, &h->arena}) if (b->p) (void)hipFree(b->p);
     for (HostBuf *b : {&h->arena_pin, &h->shared_pin[0], &h->shared_pin[1]}) {
         if (b->p) (void)hipHostFree(b->p);
         if (b->ev) (void)hipEventDestroy(b->ev);
@@ -238,7 +236,7 @@ int lqmpc_get_options(const lqmpc_handle *h, lqmpc_options *opt)
 
 int lqmpc_has_specialization(int nx, int nu, int N) { return lqmpc::spec_available(nx, nu, N) ? 1 : 0; }
 
-const char *lqmpc_last_kernel(const lqmpc_handle *h) { return h ? h->last_kernel : "none"; }
+const char *lqmpc_last_kernel(const lqmpc_handle *h) { return h ? h->last_kernel.c_str() : "none"; }
 
 }  // extern "C"
 
@@ -255,114 +253,17 @@ static int check_dims(int nx, int nu, int N, int64_t Bsz)
     return 0;
 }
 
-// small host-side dense helpers for the batch-shared weights (lqmpc_bounds_batch): SPD inverse, extreme eigenvalues
-static bool host_spd_inverse(std::vector<double> &M, int n)
-{
-    for (int k = 0; k < n; ++k) {
-        const double d = M[k * n + k];
-        if (!(d > 0.0) || !std::isfinite(d)) return false;
-        const double p = 1.0 / d;
-        M[k * n + k] = 1.0;
-        for (int j = 0; j < n; ++j) M[k * n + j] *= p;
-        for (int i = 0; i < n; ++i) {
-            if (i == k) continue;
-            const double f = M[i * n + k];
-            M[i * n + k] = 0.0;
-            for (int j = 0; j < n; ++j) M[i * n + j] -= f * M[k * n + j];
-        }
-    }
-    return true;
-}
-
-static bool host_sym_eig_extremes(const double *Min, int n, double &emax, double &emin)
-{
-    std::vector<double> M(Min, Min + n * n);
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < i; ++j)
-            if (std::fabs(M[i * n + j] - M[j * n + i]) > 1e-12 * (std::fabs(M[i * n + i]) + std::fabs(M[j * n + j]))) return false;
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0, dg = 0.0;
-        for (int p = 0; p < n; ++p) {
-            dg += M[p * n + p] * M[p * n + p];
-            for (int q = p + 1; q < n; ++q) off += M[p * n + q] * M[p * n + q];
-        }
-        if (!(off > 1e-32 * (dg + off))) break;
-        for (int p = 0; p < n - 1; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double apq = M[p * n + q];
-                if (std::fabs(apq) < 1e-300) continue;
-                const double theta = (M[q * n + q] - M[p * n + p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < n; ++k) {
-                    const double akp = M[k * n + p], akq = M[k * n + q];
-                    M[k * n + p] = c * akp - s * akq; M[k * n + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double apk = M[p * n + k], aqk = M[q * n + k];
-                    M[p * n + k] = c * apk - s * aqk; M[q * n + k] = s * apk + c * aqk;
-                }
-            }
-    }
-    emax = -1e308; emin = 1e308;
-    for (int p = 0; p < n; ++p) { emax = std::max(emax, M[p * n + p]); emin = std::min(emin, M[p * n + p]); }
-    return std::isfinite(emax) && std::isfinite(emin);
-}
-
-// First gain K_0 of the N-stage problem on (A, B): S_N = P, K_j = (R + B'S B)^-1 B'S A, S <- Q + A'S (A - B K_j).  Row-major, nu x nx.
-// (Host, once per call of a rollout with a shared plant: the difficulty order's roll uses it; 10 x O(nx^3) flops.)
-static bool host_first_gain(int nx, int nu, int N, const double *A, const double *B, const double *Q, const double *R, const double *P, double *K)
-{
-    std::vector<double> S(P, P + nx * nx), SA(nx * nx), SB(nx * nu), Re(nu * nu), F(nu * nx), Acl(nx * nx), T(nx * nx);
-    for (int j = 0; j < N; ++j) {
-        for (int a = 0; a < nx; ++a) {
-            for (int c = 0; c < nx; ++c) { double t = 0.0; for (int k = 0; k < nx; ++k) t += S[a * nx + k] * A[k * nx + c]; SA[a * nx + c] = t; }
-            for (int c = 0; c < nu; ++c) { double t = 0.0; for (int k = 0; k < nx; ++k) t += S[a * nx + k] * B[k * nu + c]; SB[a * nu + c] = t; }
-        }
-        for (int r = 0; r < nu; ++r) {
-            for (int c = 0; c < nu; ++c) { double t = R[r * nu + c]; for (int k = 0; k < nx; ++k) t += B[k * nu + r] * SB[k * nu + c]; Re[r * nu + c] = t; }
-            for (int c = 0; c < nx; ++c) { double t = 0.0; for (int k = 0; k < nx; ++k) t += B[k * nu + r] * SA[k * nx + c]; F[r * nx + c] = t; }
-        }
-        // K = Re^-1 F by Gaussian elimination with partial pivoting (nu <= 8)
-        for (int col = 0; col < nu; ++col) {
-            int piv = col;
-            for (int r = col + 1; r < nu; ++r) if (std::fabs(Re[r * nu + col]) > std::fabs(Re[piv * nu + col])) piv = r;
-            if (!(std::fabs(Re[piv * nu + col]) > 0.0)) return false;
-            if (piv != col) {
-                for (int c = 0; c < nu; ++c) std::swap(Re[piv * nu + c], Re[col * nu + c]);
-                for (int c = 0; c < nx; ++c) std::swap(F[piv * nx + c], F[col * nx + c]);
-            }
-            const double inv = 1.0 / Re[col * nu + col];
-            for (int r = 0; r < nu; ++r) {
-                if (r == col) continue;
-                const double f = Re[r * nu + col] * inv;
-                for (int c = 0; c < nu; ++c) Re[r * nu + c] -= f * Re[col * nu + c];
-                for (int c = 0; c < nx; ++c) F[r * nx + c] -= f * F[col * nx + c];
-            }
-        }
-        for (int r = 0; r < nu; ++r) { const double inv = 1.0 / Re[r * nu + r]; for (int c = 0; c < nx; ++c) K[r * nx + c] = F[r * nx + c] * inv; }
-        for (int a = 0; a < nx; ++a)
-            for (int c = 0; c < nx; ++c) { double t = A[a * nx + c]; for (int k = 0; k < nu; ++k) t -= B[a * nu + k] * K[k * nx + c]; Acl[a * nx + c] = t; }
-        for (int a = 0; a < nx; ++a)
-            for (int c = 0; c < nx; ++c) { double t = 0.0; for (int k = 0; k < nx; ++k) t += S[a * nx + k] * Acl[k * nx + c]; T[a * nx + c] = t; }
-        for (int a = 0; a < nx; ++a)
-            for (int c = 0; c < nx; ++c) { double t = Q[a * nx + c]; for (int k = 0; k < nx; ++k) t += A[k * nx + a] * T[k * nx + c]; S[a * nx + c] = t; }
-    }
-    for (int e = 0; e < nu * nx; ++e) if (!std::isfinite(K[e])) return false;
-    return true;
-}
-
 struct Call {
     int nx, nu, N, T, K, mode, true_per_instance;
     int64_t Bsz;
     const double *Q, *R, *P, *lb, *ub, *x_ref, *u_ref, *At_sh, *Bt_sh, *x0s;
 };
 
-// references or an off-centre box: the linear term has a constant part
+// references or an off-centre box: the linear term has a constant part (lqmpc_reserve plans without a box)
 static bool has_lin(const Call &c)
 {
     bool lin = c.x_ref || c.u_ref;
-    for (int k = 0; k < c.nu; ++k) lin = lin || (c.ub[k] + c.lb[k] != 0.0);
+    for (int k = 0; c.lb && c.ub && k < c.nu; ++k) lin = lin || (c.ub[k] + c.lb[k] != 0.0);
     return lin;
 }
 
@@ -382,6 +283,8 @@ struct Plan {
     bool order_roll;     // the host computes the first gain for the order's key (KParams::order_roll)
     long long nwide;     // FAM_SPEC_TIERED: slots of the wide tier
     long long ws_cols;   // workspace columns of the generic kernel; 0: the call needs no workspace
+    int presolve, warm_start;   // options.presolve / warm_start with their defaults resolved
+    bool has_lin;        // has_lin() of the call
     // the 16-lane-row kernels on the whole batch: every mode, the sweep fused into one launch (otherwise it is the two-launch fall-back)
     bool rows() const { return family == FAM_R16 || family == FAM_JIT; }
     // the hand-back list goes to the generic kernel over a list, with ws_cols columns (otherwise to the packed kernel)
@@ -393,7 +296,9 @@ struct Plan {
 static int make_plan(const lqmpc_options &o, const Call &c, int device, Plan &pl)
 {
     const int nx = c.nx, nu = c.nu, N = c.N;
-    const int presolve = o.presolve < 0 ? 1 : o.presolve, warm_start = o.warm_start < 0 ? presolve : o.warm_start;
+    const int presolve = pl.presolve = o.presolve < 0 ? 1 : o.presolve;
+    const int warm_start = pl.warm_start = o.warm_start < 0 ? presolve : o.warm_start;
+    pl.has_lin = has_lin(c);
     const bool built = lqmpc::spec_available(nx, nu, N);
     if (o.kernel == LQMPC_KERNEL_SPECIALIZED && !built)
         return fail(LQMPC_ERR_UNSUPPORTED, "no register-resident specialisation built for these dims");
@@ -438,7 +343,7 @@ static int make_plan(const lqmpc_options &o, const Call &c, int device, Plan &pl
     // PLANT under the first gain of the N-stage problem on it -- the closed loop every instance of the batch runs in.  Only where an
     // order can be built at all (the looser of the two sizes): small batches skip the host's Riccati steps.
     const bool may_order = o.order > 0 || (o.order < 0 && packed_size);
-    pl.order_roll = may_order && rollout && nu <= 8 && !c.true_per_instance && c.At_sh && c.Bt_sh && !has_lin(c);
+    pl.order_roll = may_order && rollout && nu <= 8 && !c.true_per_instance && c.At_sh && c.Bt_sh && !pl.has_lin;
     // the hardest instances (first in the order) in the 16-lane-row layout: see lqmpc_spec_tiered_kernel
     pl.nwide = 0;
     if (pl.order && pl.family == FAM_SPEC && lqmpc::spec_tiered_available(nx, nu, N) && presolve && warm_start && c.Bsz <= INT32_MAX) {
@@ -536,10 +441,9 @@ static int prepare(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, KPa
     p.T = c.T; p.K = c.K; p.mode = c.mode;
     p.true_per_instance = c.true_per_instance;
     p.has_ref = (c.x_ref || c.u_ref) ? 1 : 0;
-    p.has_lin = has_lin(c) ? 1 : 0;
+    p.has_lin = pl.has_lin ? 1 : 0;
     p.max_iter = opt.max_iter; p.polish = opt.polish;
-    p.presolve = opt.presolve < 0 ? 1 : opt.presolve;
-    p.warm_start = opt.warm_start < 0 ? p.presolve : opt.warm_start;
+    p.presolve = pl.presolve; p.warm_start = pl.warm_start;
     p.eps = opt.eps; p.tau = opt.tau; p.z0_scale = opt.z0_scale;
     p.Bsz = c.Bsz;
     p.sh = (const double *)h->shared.p;
@@ -604,6 +508,13 @@ static int build_order(lqmpc_handle *h, const Plan &pl, KParams &p)
     return 0;
 }
 
+// what lqmpc_last_kernel reports: a copy of the name, and which controller's record path it came from (0: none)
+static void set_last_kernel(lqmpc_handle *h, const char *name, uint64_t owner = 0)
+{
+    h->last_kernel = name;
+    h->last_owner = owner;
+}
+
 // one launch of the packed, workgroup or generic kernel on the whole batch
 static int launch(lqmpc_handle *h, const Plan &pl, const KParams &p)
 {
@@ -615,7 +526,7 @@ static int launch(lqmpc_handle *h, const Plan &pl, const KParams &p)
     } else {
         lqmpc::launch_generic(p, h->stream);
     }
-    h->last_kernel = name;
+    set_last_kernel(h, name);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -688,7 +599,7 @@ static int launch_rows(lqmpc_handle *h, const Plan &pl, KParams &p)
                            (const int *)h->st2.p, (const int *)h->it2.p, (const int *)p.fail_list, (const int *)p.fail_count);
         HIP_TRY(hipGetLastError());
     }
-    h->last_kernel = name;
+    set_last_kernel(h, name);
     return 0;
 }
 
@@ -700,6 +611,21 @@ __global__ void lqmpc_merge_status_kernel(int *st, int *it, const int *st2, cons
     if (it) it[i] += it2[i];
 }
 
+// Every launch of a planned one-shot call whose parameter block is filled: the difficulty order where planned, then the 16-lane-row
+// family with its hand-back pass, the two tiers of a sorted packed rollout, or the one launch of the packed, workgroup or generic kernel.
+static int run(lqmpc_handle *h, const Plan &pl, KParams &p)
+{
+    int rc = pl.order ? build_order(h, pl, p) : 0;
+    if (rc) return rc;
+    if (pl.rows()) return launch_rows(h, pl, p);
+    if (pl.family != FAM_SPEC_TIERED) return launch(h, pl, p);
+    p.nwide = pl.nwide;
+    rc = prepare_hand_back(h, p);
+    if (!rc) rc = launch(h, pl, p);
+    // second pass: whatever the wide tier handed back (status 3), packed, from the start of the rollout
+    return rc ? rc : launch_hand_back(h, pl, p, p.mode, nullptr);
+}
+
 // lqmpc_solve_batch_dev under explicit options (a prepared controller passes through here under its own snapshot)
 static int solve_dev(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, const double *dA, const double *dB, const double *dx0,
                      double *du0, double *dVN, int32_t *dstatus, int32_t *diters)
@@ -709,7 +635,7 @@ static int solve_dev(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, c
     int rc = prepare(h, opt, c, p, pl);
     if (rc) return rc;
     p.A = dA; p.B = dB; p.x0 = dx0; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
-    return pl.rows() ? launch_rows(h, pl, p) : launch(h, pl, p);
+    return run(h, pl, p);
 }
 
 // lqmpc_rollout_batch_dev under explicit options (a prepared controller passes through here under its own snapshot)
@@ -722,17 +648,7 @@ static int rollout_dev(lqmpc_handle *h, const lqmpc_options &opt, const Call &c,
     if (rc) return rc;
     p.A = dA; p.B = dB; p.x0 = dx0; p.JT = dJT; p.X = dX; p.U = dU; p.status = dstatus; p.iters = diters;
     if (c.true_per_instance) { p.At = A_true; p.Bt = B_true; }
-    if (pl.order) {
-        rc = build_order(h, pl, p);
-        if (rc) return rc;
-    }
-    if (pl.rows()) return launch_rows(h, pl, p);
-    if (pl.family != FAM_SPEC_TIERED) return launch(h, pl, p);
-    p.nwide = pl.nwide;
-    rc = prepare_hand_back(h, p);
-    if (!rc) rc = launch(h, pl, p);
-    // second pass: whatever the wide tier handed back (status 3), packed, from the start of the rollout
-    return rc ? rc : launch_hand_back(h, pl, p, p.mode, nullptr);
+    return run(h, pl, p);
 }
 
 extern "C" {
@@ -793,7 +709,7 @@ int lqmpc_max_vn_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, 
     int rc = prepare(h, h->opt, c, p, pl);
     if (rc) return rc;
     p.A = dA; p.B = dB; p.MV = dMV; p.status = dstatus; p.iters = diters;
-    return pl.rows() ? launch_rows(h, pl, p) : launch(h, pl, p);
+    return run(h, pl, p);
 }
 
 int lqmpc_sweep_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, int K, const double *dA, const double *dB,
@@ -814,11 +730,7 @@ int lqmpc_sweep_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, i
         // one launch: condensing and W once per instance, K open-loop QPs, then the closed loop
         p.A = dA; p.B = dB; p.x0 = dx0; p.JT = dJT; p.MV = dMV; p.status = dstatus; p.iters = diters;
         if (true_per_instance) { p.At = A_true; p.Bt = B_true; }
-        if (pl.order) {
-            rc = build_order(h, pl, p);
-            if (rc) return rc;
-        }
-        return launch_rows(h, pl, p);
+        return run(h, pl, p);
     }
     // no fused kernel for this shape / size: the two launches (each plans for itself), status = worse of the two, iters = their sum
     int32_t *st2 = nullptr, *it2 = nullptr;
@@ -841,89 +753,70 @@ int lqmpc_sweep_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, i
 
 // ---- host-buffer flavours: stage in, run, stage out ----
 namespace {
+// An entry point names each of its arrays once -- in() / out() with the host pointer, the element count and the variable that takes
+// the device pointer -- then upload(), the launches, finish().  From upload() on the variables hold the device addresses (NULL for a
+// NULL host pointer, which is not copied either); finish() brings the outputs back and waits for the stream.  All arrays of a call
+// share one device block laid out by lqmpc::ArenaLayout, which grows as needed.
 // Small calls (the reference's own call shape is ONE instance per solve(), utils_class.py:269) are dominated by the number of
-// copies, not their size: below PACK_LIMIT bytes in total every array of the call is packed into one pinned host block and one
-// device block -- one copy in, one copy out.  Larger calls copy array by array straight from / to the caller's buffers.
+// copies, not their size: up to PACK_LIMIT bytes in total the block has a pinned host image -- one copy in, one copy out.  Larger
+// calls copy array by array straight from / to the caller's buffers.
 constexpr size_t PACK_LIMIT = 256 * 1024;
 struct Stager {
     lqmpc_handle *h;
-    int slot = 0;
-    int rc = 0;
+    lqmpc::ArenaLayout lay;
+    struct Arr { void *host; void *var; void (*set)(void *var, char *dev); };
+    std::vector<Arr> arrs;                                        // one per slot of lay
+    bool may_pack = true;                                         // false: array by array whatever the size
     bool packed = false;
-    size_t off = 0, in_end = 0;
-    struct Out { void *host; size_t off, bytes; } outs[12];
-    int nout = 0;
-    // total: an upper bound of the bytes of all in() / out() arrays of the call
-    void begin(size_t total)
+
+    template <typename T>
+    void add(T *host, size_t count, T *&dev, bool out)
     {
-        total += 24 * 256;
-        if (total > PACK_LIMIT) return;
-        rc = ensure(h, h->arena, total);
-        if (!rc) rc = ensure_host(h->arena_pin, total);
-        if (rc) return;
-        if (h->arena_pin.ev_valid) { (void)hipEventSynchronize(h->arena_pin.ev); h->arena_pin.ev_valid = false; }
-        packed = true;
+        dev = nullptr;
+        if (arrs.empty()) { arrs.reserve(16); lay.slots.reserve(16); }      // (one allocation each for every entry point there is)
+        lay.add(count * sizeof(T), out, host != nullptr);
+        arrs.push_back(Arr{(void *)host, &dev, [](void *var, char *d) { *(T **)var = (T *)d; }});
     }
-    size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255) / 256 * 256; return o; }
-    // after the last in(): the one copy of the inputs
-    void upload()
+    template <typename T> void in(const T *host, size_t count, const T *&dev) { add(host, count, dev, false); }
+    template <typename T> void out(T *host, size_t count, T *&dev) { add(host, count, dev, true); }
+    int copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, const char *what)
     {
-        if (rc || !packed) return;
-        if (nout == 0) in_end = off;                              // (the first out() froze it otherwise)
-        if (in_end == 0) return;
-        hipError_t e = hipMemcpyAsync(h->arena.p, h->arena_pin.p, in_end, hipMemcpyHostToDevice, h->stream);
-        if (e != hipSuccess) rc = fail(LQMPC_ERR_HIP, std::string("H2D: ") + hipGetErrorString(e));
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, h->stream);
+        return e == hipSuccess ? 0 : fail(LQMPC_ERR_HIP, std::string(what) + hipGetErrorString(e));
     }
-    // after the launches: the one copy of the outputs, the wait, and the hand-over to the caller's arrays
+    // after the last in() / out(): room for everything, the inputs on their way
+    int upload()
+    {
+        lay.place();
+        packed = may_pack && lay.total <= PACK_LIMIT;
+        int rc = ensure(h, h->arena, lay.total);
+        if (!rc && packed) rc = ensure_host(h->arena_pin, lay.total);
+        char *dev = (char *)h->arena.p, *pin = (char *)h->arena_pin.p;
+        for (size_t k = 0; !rc && k < arrs.size(); ++k) {
+            const lqmpc::ArenaLayout::Slot &sl = lay.slots[k];
+            if (!sl.present) continue;
+            arrs[k].set(arrs[k].var, dev + sl.off);
+            if (sl.out) continue;
+            if (packed) memcpy(pin + sl.off, arrs[k].host, sl.bytes);
+            else rc = copy(dev + sl.off, arrs[k].host, sl.bytes, hipMemcpyHostToDevice, "H2D: ");
+        }
+        if (!rc && packed && lay.in_end) rc = copy(dev, pin, lay.in_end, hipMemcpyHostToDevice, "H2D: ");
+        return rc;
+    }
+    // after the launches: the outputs on their way back, the wait, and (packed) the hand-over to the caller's arrays
     int finish()
     {
+        char *dev = (char *)h->arena.p, *pin = (char *)h->arena_pin.p;
+        int rc = 0;
+        if (packed && lay.total > lay.in_end) rc = copy(pin + lay.in_end, dev + lay.in_end, lay.total - lay.in_end, hipMemcpyDeviceToHost, "D2H: ");
+        for (size_t k = 0; !packed && !rc && k < arrs.size(); ++k)
+            if (lay.slots[k].present && lay.slots[k].out) rc = copy(arrs[k].host, dev + lay.slots[k].off, lay.slots[k].bytes, hipMemcpyDeviceToHost, "D2H: ");
         if (rc) return rc;
-        if (packed && nout > 0) {
-            hipError_t e = hipMemcpyAsync((char *)h->arena_pin.p + in_end, (char *)h->arena.p + in_end, off - in_end, hipMemcpyDeviceToHost, h->stream);
-            if (e != hipSuccess) return fail(LQMPC_ERR_HIP, std::string("D2H: ") + hipGetErrorString(e));
-        }
-        hipError_t e = hipStreamSynchronize(h->stream);
+        const hipError_t e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) return fail(LQMPC_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-        if (packed)
-            for (int k = 0; k < nout; ++k) memcpy(outs[k].host, (char *)h->arena_pin.p + outs[k].off, outs[k].bytes);
+        for (size_t k = 0; packed && k < arrs.size(); ++k)
+            if (lay.slots[k].present && lay.slots[k].out) memcpy(arrs[k].host, pin + lay.slots[k].off, lay.slots[k].bytes);
         return 0;
-    }
-    template <typename T>
-    T *in(const T *host, size_t count)
-    {
-        if (rc || !host) return nullptr;
-        if (packed) {
-            const size_t o = take(count * sizeof(T));
-            memcpy((char *)h->arena_pin.p + o, host, count * sizeof(T));
-            return (T *)((char *)h->arena.p + o);
-        }
-        DevBuf &b = h->stage[slot++];
-        rc = ensure(h, b, count * sizeof(T));
-        if (rc) return nullptr;
-        hipError_t e = hipMemcpyAsync(b.p, host, count * sizeof(T), hipMemcpyHostToDevice, h->stream);
-        if (e != hipSuccess) { rc = fail(LQMPC_ERR_HIP, std::string("H2D: ") + hipGetErrorString(e)); return nullptr; }
-        return (T *)b.p;
-    }
-    template <typename T>
-    T *out(T *host, size_t count)
-    {
-        if (rc || !host) return nullptr;
-        if (packed) {
-            if (nout == 0 && in_end == 0) in_end = off;           // (a call without inputs to upload)
-            const size_t o = take(count * sizeof(T));
-            outs[nout++] = Out{host, o, count * sizeof(T)};
-            return (T *)((char *)h->arena.p + o);
-        }
-        DevBuf &b = h->stage[slot++];
-        rc = ensure(h, b, count * sizeof(T));
-        return rc ? nullptr : (T *)b.p;
-    }
-    template <typename T>
-    void back(T *host, const T *dev, size_t count)
-    {
-        if (rc || !host || packed) return;                        // packed: finish() copies everything back at once
-        hipError_t e = hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, h->stream);
-        if (e != hipSuccess) rc = fail(LQMPC_ERR_HIP, std::string("D2H: ") + hipGetErrorString(e));
     }
 };
 }  // namespace
@@ -941,16 +834,14 @@ int lqmpc_solve_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const
     HIP_TRY(hipSetDevice(h->device));
     Stager s{h};
     const size_t b = (size_t)Bsz;
-    s.begin(b * 8 * (size_t)(nx * nx + nx * nu + nx + nu + 2));
-    const double *dA = s.in(A, b * nx * nx), *dB = s.in(B, b * nx * nu), *dx0 = s.in(x0, b * nx);
-    double *du0 = s.out(u0, b * nu), *dVN = s.out(VN, b);
-    int32_t *dst = s.out(status, b), *dit = s.out(iters, b);
-    s.upload();
-    if (s.rc) return s.rc;
-    rc = lqmpc_solve_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dx0, x_ref, u_ref, du0, dVN, dst, dit);
-    if (rc) return rc;
-    s.back(u0, du0, b * nu); s.back(VN, dVN, b); s.back(status, dst, b); s.back(iters, dit, b);
-    return s.finish();
+    const double *dA, *dB, *dx0;
+    double *du0, *dVN;
+    int32_t *dst, *dit;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(x0, b * nx, dx0);
+    s.out(u0, b * nu, du0); s.out(VN, b, dVN); s.out(status, b, dst); s.out(iters, b, dit);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_solve_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dx0, x_ref, u_ref, du0, dVN, dst, dit);
+    return rc ? rc : s.finish();
 }
 
 int lqmpc_rollout_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *A, const double *B,
@@ -966,20 +857,16 @@ int lqmpc_rollout_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int
     HIP_TRY(hipSetDevice(h->device));
     Stager s{h};
     const size_t b = (size_t)Bsz;
-    s.begin(b * 8 * (size_t)(2 * (nx * nx + nx * nu) + nx + 2 + (X ? nx * (T + 1) : 0) + (U ? nu * T : 0)));
-    const double *dA = s.in(A, b * nx * nx), *dB = s.in(B, b * nx * nu), *dx0 = s.in(x0, b * nx);
-    const double *dAt = A_true, *dBt = B_true;
-    if (true_per_instance) { dAt = s.in(A_true, b * nx * nx); dBt = s.in(B_true, b * nx * nu); }
-    double *dJT = s.out(JT, b), *dX = s.out(X, b * nx * (T + 1)), *dU = s.out(U, b * nu * T);
-    int32_t *dst = s.out(status, b), *dit = s.out(iters, b);
-    s.upload();
-    if (s.rc) return s.rc;
-    rc = lqmpc_rollout_batch_dev(h, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dx0, dAt, dBt, true_per_instance, x_ref,
-                                 u_ref, dJT, dX, dU, dst, dit);
-    if (rc) return rc;
-    s.back(JT, dJT, b); s.back(X, dX, b * nx * (T + 1)); s.back(U, dU, b * nu * T);
-    s.back(status, dst, b); s.back(iters, dit, b);
-    return s.finish();
+    const double *dA, *dB, *dx0, *dAt = A_true, *dBt = B_true;
+    double *dJT, *dX, *dU;
+    int32_t *dst, *dit;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(x0, b * nx, dx0);
+    if (true_per_instance) { s.in(A_true, b * nx * nx, dAt); s.in(B_true, b * nx * nu, dBt); }
+    s.out(JT, b, dJT); s.out(X, b * nx * (T + 1), dX); s.out(U, b * nu * T, dU); s.out(status, b, dst); s.out(iters, b, dit);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_rollout_batch_dev(h, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dx0, dAt, dBt, true_per_instance, x_ref,
+                                          u_ref, dJT, dX, dU, dst, dit);
+    return rc ? rc : s.finish();
 }
 
 int lqmpc_max_vn_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int K, const double *A, const double *B,
@@ -993,16 +880,14 @@ int lqmpc_max_vn_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int 
     HIP_TRY(hipSetDevice(h->device));
     Stager s{h};
     const size_t b = (size_t)Bsz;
-    s.begin(b * 8 * (size_t)(nx * nx + nx * nu + 2));
-    const double *dA = s.in(A, b * nx * nx), *dB = s.in(B, b * nx * nu);
-    double *dMV = s.out(MV, b);
-    int32_t *dst = s.out(status, b), *dit = s.out(iters, b);
-    s.upload();
-    if (s.rc) return s.rc;
-    rc = lqmpc_max_vn_batch_dev(h, nx, nu, N, Bsz, K, dA, dB, Q, R, P, lb, ub, x0s, x_ref, u_ref, dMV, dst, dit);
-    if (rc) return rc;
-    s.back(MV, dMV, b); s.back(status, dst, b); s.back(iters, dit, b);
-    return s.finish();
+    const double *dA, *dB;
+    double *dMV;
+    int32_t *dst, *dit;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB);
+    s.out(MV, b, dMV); s.out(status, b, dst); s.out(iters, b, dit);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_max_vn_batch_dev(h, nx, nu, N, Bsz, K, dA, dB, Q, R, P, lb, ub, x0s, x_ref, u_ref, dMV, dst, dit);
+    return rc ? rc : s.finish();
 }
 
 int lqmpc_sweep_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, int K, const double *A, const double *B,
@@ -1016,19 +901,16 @@ int lqmpc_sweep_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T
     HIP_TRY(hipSetDevice(h->device));
     Stager s{h};
     const size_t b = (size_t)Bsz;
-    s.begin(b * 8 * (size_t)(2 * (nx * nx + nx * nu) + nx + 3));
-    const double *dA = s.in(A, b * nx * nx), *dB = s.in(B, b * nx * nu), *dx0 = s.in(x0, b * nx);
-    const double *dAt = A_true, *dBt = B_true;
-    if (true_per_instance) { dAt = s.in(A_true, b * nx * nx); dBt = s.in(B_true, b * nx * nu); }
-    double *dJT = s.out(JT, b), *dMV = s.out(MV, b);
-    int32_t *dst = s.out(status, b), *dit = s.out(iters, b);
-    s.upload();
-    if (s.rc) return s.rc;
-    rc = lqmpc_sweep_batch_dev(h, nx, nu, N, Bsz, T, K, dA, dB, Q, R, P, lb, ub, dx0, x0s, dAt, dBt, true_per_instance, x_ref, u_ref,
-                               dJT, dMV, dst, dit);
-    if (rc) return rc;
-    s.back(JT, dJT, b); s.back(MV, dMV, b); s.back(status, dst, b); s.back(iters, dit, b);
-    return s.finish();
+    const double *dA, *dB, *dx0, *dAt = A_true, *dBt = B_true;
+    double *dJT, *dMV;
+    int32_t *dst, *dit;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(x0, b * nx, dx0);
+    if (true_per_instance) { s.in(A_true, b * nx * nx, dAt); s.in(B_true, b * nx * nu, dBt); }
+    s.out(JT, b, dJT); s.out(MV, b, dMV); s.out(status, b, dst); s.out(iters, b, dit);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_sweep_batch_dev(h, nx, nu, N, Bsz, T, K, dA, dB, Q, R, P, lb, ub, dx0, x0s, dAt, dBt, true_per_instance, x_ref,
+                                        u_ref, dJT, dMV, dst, dit);
+    return rc ? rc : s.finish();
 }
 
 // ---- the bound coefficients of data_generation: lqmpc_bounds.hip ----
@@ -1095,7 +977,7 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, 
         }
         if (done) {
             HIP_TRY(hipGetLastError());
-            h->last_kernel = "lqmpc_bounds_small_kernel + lqmpc_bounds_big_kernel";
+            set_last_kernel(h, "lqmpc_bounds_small_kernel + lqmpc_bounds_big_kernel");
             return 0;
         }
     }
@@ -1112,7 +994,7 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, 
         lqmpc::launch_bounds(bp, h->stream);
         HIP_TRY(hipGetLastError());
     }
-    h->last_kernel = "lqmpc_bounds_kernel";
+    set_last_kernel(h, "lqmpc_bounds_kernel");
     return 0;
 }
 
@@ -1126,23 +1008,19 @@ int lqmpc_bounds_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, cons
     int rc = check_dims(nx, nu, N, Bsz);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(h->device));
-    // (the workspace of the kernel is h->ws; staging uses its own buffers.  Twelve staging slots are in use at most.)
     Stager s{h};
+    s.may_pack = false;                                  // (as this entry point always has: its copies are not the cost of a call)
     const size_t b = (size_t)Bsz;
-    const double *dA = s.in(A, b * nx * nx), *dB = s.in(B, b * nx * nu), *deA = s.in(e_A, b), *deB = s.in(e_B, b), *dMV = s.in(MV, b);
-    double *dK = s.out(K, b * nu * nx), *dal = s.out(alpha, b), *dbe = s.out(beta, b), *dxi = s.out(xi, b), *det = s.out(eta, b);
-    double *dbd = s.out(bound, b), *dep = s.out(eps, b);
-    if (s.rc) return s.rc;
-    // aux (8 doubles per instance) and status share no staging slot with the above: reuse the ordering buffers of the solver
-    double *dax = nullptr; int32_t *dst = nullptr;
-    if (aux) { rc = ensure(h, h->rec, b * 8 * sizeof(double)); if (rc) return rc; dax = (double *)h->rec.p; }
-    if (status) { rc = ensure(h, h->st2, b * sizeof(int32_t)); if (rc) return rc; dst = (int32_t *)h->st2.p; }
-    rc = lqmpc_bounds_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, lb, ub, deA, deB, dMV, x, p3, V_expert, dK, dal, dbe, dxi, det, dbd, dep,
-                                dax, dst);
-    if (rc) return rc;
-    s.back(K, dK, b * nu * nx); s.back(alpha, dal, b); s.back(beta, dbe, b); s.back(xi, dxi, b); s.back(eta, det, b);
-    s.back(bound, dbd, b); s.back(eps, dep, b); s.back(aux, dax, b * 8); s.back(status, dst, b);
-    return s.finish();
+    const double *dA, *dB, *deA, *deB, *dMV;
+    double *dK, *dal, *dbe, *dxi, *det, *dbd, *dep, *dax;
+    int32_t *dst;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(e_A, b, deA); s.in(e_B, b, deB); s.in(MV, b, dMV);
+    s.out(K, b * nu * nx, dK); s.out(alpha, b, dal); s.out(beta, b, dbe); s.out(xi, b, dxi); s.out(eta, b, det);
+    s.out(bound, b, dbd); s.out(eps, b, dep); s.out(aux, b * 8, dax); s.out(status, b, dst);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_bounds_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, lb, ub, deA, deB, dMV, x, p3, V_expert, dK, dal, dbe, dxi, det, dbd,
+                                         dep, dax, dst);
+    return rc ? rc : s.finish();
 }
 
 int lqmpc_timer_begin(lqmpc_handle *h)
@@ -1167,6 +1045,7 @@ int lqmpc_timer_end(lqmpc_handle *h, float *ms)
 // Prepared controllers: the per-instance set-up kept in HBM, one QP per instance and call from it (kernels: lqmpc_ctl.hip).
 struct lqmpc_controller {
     lqmpc_handle *h = nullptr;
+    uint64_t id = 0;                          // what the handle remembers of the controller that set last_kernel
     lqmpc_options opt;                        // the handle's options when the controller was made: every step is planned and filled from these
     int nx = 0, nu = 0, N = 0;
     int64_t Bsz = 0;
@@ -1218,13 +1097,49 @@ int ctl_launch(lqmpc_controller *c, const KParams &p)
     return 0;
 }
 
+// per instance: the words of its face entry, the doubles of its record
+struct CtlSizes { size_t face_words, stride; };
+CtlSizes ctl_sizes(const lqmpc_controller *c)
+{
+    if (c->wg) return {(size_t)(lqmpc::WG_CTL_FACE_WORDS + 2 * c->nx), (size_t)lqmpc::wg_ctl_rec_layout(c->nx, c->nu, c->N).stride};
+    return {(size_t)(2 + 2 * c->nx), (size_t)lqmpc::ctl_rec_layout(c->nx, c->nu, c->N).stride};
+}
+
 void ctl_bind(const lqmpc_controller *c, KParams &p)
 {
     p.A = (const double *)c->A; p.B = (const double *)c->B;
     p.ctl_rec = (double *)c->rec;
-    p.ctl_stride = c->wg ? lqmpc::wg_ctl_rec_layout(c->nx, c->nu, c->N).stride : lqmpc::ctl_rec_layout(c->nx, c->nu, c->N).stride;
+    p.ctl_stride = (long long)ctl_sizes(c).stride;
     p.ctl_face = (unsigned long long *)c->face;
     p.ctl_idx = nullptr; p.ctl_n = c->Bsz;
+}
+
+// the argument checks, the shared block and the plan of `cl` on the controller's handle under its option snapshot, as at create and
+// at every step; the parameter block bound to its records and copies
+int ctl_prepare(const lqmpc_controller *c, const Call &cl, KParams &p, Plan &pl)
+{
+    const int rc = prepare(c->h, c->opt, cl, p, pl);
+    if (!rc) ctl_bind(c, p);
+    return rc;
+}
+
+// V_N of a step whose caller passed NULL: allocated on first need
+int ctl_vn(lqmpc_controller *c) { return c->vn ? 0 : ctl_alloc(c, &c->vn, (size_t)c->Bsz * sizeof(double)); }
+
+// One record-path call with `p` filled: the launch on the records, then whatever it handed back -- the instances that did not settle
+// within r16_maxit iterations or met a non-finite state -- from scratch in mode `hand_back` on the existing kernels, over the
+// device-side list and from the controller's copies of A and B, as launch_rows does for a one-shot call.  The workgroup records hand
+// nothing back: their fall-back (interior point on the n x n matrices) is inside solve_qp, one launch.
+int ctl_run(lqmpc_controller *c, const Plan &pl, KParams &p, int hand_back, bool need_vn, const std::string &name)
+{
+    lqmpc_handle *h = c->h;
+    const bool list = !c->wg;
+    int rc = list ? prepare_hand_back(h, p) : 0;
+    if (!rc) rc = ctl_launch(c, p);
+    if (!rc && list && need_vn) rc = ctl_vn(c);
+    if (!rc && list) rc = launch_hand_back(h, pl, p, hand_back, need_vn ? (double *)c->vn : nullptr);
+    if (!rc) set_last_kernel(h, name.c_str(), c->id);
+    return rc;
 }
 
 int ctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B, hipMemcpyKind kind, const double *Q,
@@ -1240,7 +1155,7 @@ int ctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double
     int rc = prepare(h, h->opt, c0, p, pl);
     if (rc) return rc;
     lqmpc_controller *c = new lqmpc_controller();
-    c->h = h; c->opt = h->opt; c->nx = nx; c->nu = nu; c->N = N; c->Bsz = Bsz;
+    c->h = h; c->id = ++h->ctl_ids; c->opt = h->opt; c->nx = nx; c->nu = nu; c->N = N; c->Bsz = Bsz;
     c->Q.assign(Q, Q + nx * nx); c->R.assign(R, R + nu * nu); c->P.assign(P, P + nx * nx);
     c->lb.assign(lb, lb + nu); c->ub.assign(ub, ub + nu);
     if (x_ref) { c->xref.assign(x_ref, x_ref + nx * N); c->has_xref = true; }
@@ -1258,8 +1173,7 @@ int ctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double
         // opt-in (a record is two images of the block triangle: 166 KB per instance at (8,4,30)): records on the workgroup kernel's shapes
         c->fast = c->wg = true;
     }
-    const size_t face_words = c->wg ? (size_t)(lqmpc::WG_CTL_FACE_WORDS + 2 * nx) : (size_t)(2 + 2 * nx);
-    const size_t rec_doubles = c->wg ? (size_t)lqmpc::wg_ctl_rec_layout(nx, nu, N).stride : (size_t)lqmpc::ctl_rec_layout(nx, nu, N).stride;
+    const size_t face_words = ctl_sizes(c).face_words, rec_doubles = ctl_sizes(c).stride;
     const size_t b = (size_t)Bsz, nA = b * nx * nx * sizeof(double), nB = b * nx * nu * sizeof(double);
     rc = ctl_alloc(c, &c->A, nA);
     if (!rc) rc = ctl_alloc(c, &c->B, nB);
@@ -1324,35 +1238,18 @@ int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0
     const Call cl = ctl_call(c);
     if (!c->fast) {
         // pass-through: the existing solve path, unchanged, on the controller's copies of A and B
-        if (!dVN && !c->vn) { int rc = ctl_alloc(c, &c->vn, (size_t)c->Bsz * sizeof(double)); if (rc) return rc; }
-        int rc = solve_dev(h, c->opt, cl, (const double *)c->A, (const double *)c->B, dx, du0, dVN ? dVN : (double *)c->vn, dstatus, diters);
+        int rc = dVN ? 0 : ctl_vn(c);
+        if (!rc) rc = solve_dev(h, c->opt, cl, (const double *)c->A, (const double *)c->B, dx, du0, dVN ? dVN : (double *)c->vn, dstatus, diters);
         if (!rc) c->name = h->last_kernel;
         return rc;
     }
     KParams p;
     Plan pl;
-    int rc = prepare(h, c->opt, cl, p, pl);
+    int rc = ctl_prepare(c, cl, p, pl);
     if (rc) return rc;
-    ctl_bind(c, p);
     p.x0 = dx; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
     p.mode = lqmpc::MODE_CTL_STEP;
-    if (c->wg) {
-        // one launch: the workgroup kernel's fall-back (interior point on the n x n matrices) is inside solve_qp
-        rc = ctl_launch(c, p);
-        if (!rc) h->last_kernel = c->name.c_str();
-        return rc;
-    }
-    rc = prepare_hand_back(h, p);
-    if (rc) return rc;
-    rc = ctl_launch(c, p);
-    if (rc) return rc;
-    // whatever did not settle within r16_maxit iterations (or arrived with a non-finite state): the existing kernels, from scratch, over
-    // the device-side list -- as launch_rows does for a one-shot solve
-    if (!dVN && !c->vn) { rc = ctl_alloc(c, &c->vn, (size_t)c->Bsz * sizeof(double)); if (rc) return rc; }
-    rc = launch_hand_back(h, pl, p, lqmpc::MODE_SOLVE, (double *)c->vn);
-    if (rc) return rc;
-    h->last_kernel = c->name.c_str();
-    return 0;
+    return ctl_run(c, pl, p, lqmpc::MODE_SOLVE, !dVN, c->name);
 }
 
 int lqmpc_controller_step(lqmpc_controller *c, const double *x, double *u0, double *VN, int32_t *status, int32_t *iters)
@@ -1362,16 +1259,14 @@ int lqmpc_controller_step(lqmpc_controller *c, const double *x, double *u0, doub
     HIP_TRY(hipSetDevice(h->device));
     Stager s{h};
     const size_t b = (size_t)c->Bsz;
-    s.begin(b * 8 * (size_t)(c->nx + c->nu + 2));
-    const double *dx = s.in(x, b * c->nx);
-    double *du0 = s.out(u0, b * c->nu), *dVN = s.out(VN, b);
-    int32_t *dst = s.out(status, b), *dit = s.out(iters, b);
-    s.upload();
-    if (s.rc) return s.rc;
-    int rc = lqmpc_controller_step_dev(c, dx, du0, dVN, dst, dit);
-    if (rc) return rc;
-    s.back(u0, du0, b * c->nu); s.back(VN, dVN, b); s.back(status, dst, b); s.back(iters, dit, b);
-    return s.finish();
+    const double *dx;
+    double *du0, *dVN;
+    int32_t *dst, *dit;
+    s.in(x, b * c->nx, dx);
+    s.out(u0, b * c->nu, du0); s.out(VN, b, dVN); s.out(status, b, dst); s.out(iters, b, dit);
+    int rc = s.upload();
+    if (!rc) rc = lqmpc_controller_step_dev(c, dx, du0, dVN, dst, dit);
+    return rc ? rc : s.finish();
 }
 
 // T closed-loop steps of every instance from the controller's present state, in one launch.  Read-only on the controller: the
@@ -1414,28 +1309,14 @@ int lqmpc_controller_rollout_dev(lqmpc_controller *c, int T, const double *dx0, 
     // planned as a step is (the family of create, no order); the shared block carries a shared plant
     KParams p;
     Plan pl;
-    int rc = prepare(h, c->opt, cl, p, pl);
+    int rc = ctl_prepare(c, cl, p, pl);
     if (rc) return rc;
-    ctl_bind(c, p);
     p.ctl_face = nullptr;
     p.x0 = dx0; p.JT = dJT; p.X = dX; p.U = dU; p.status = dstatus; p.iters = diters;
     if (tpi) { p.At = A_true; p.Bt = B_true; }
     p.mode = lqmpc::MODE_CTL_ROLL;
-    if (c->wg) {
-        rc = ctl_launch(c, p);
-        if (!rc) h->last_kernel = c->roll_name.c_str();
-        return rc;
-    }
-    rc = prepare_hand_back(h, p);
-    if (rc) return rc;
-    rc = ctl_launch(c, p);
-    if (rc) return rc;
-    // whatever did not settle within r16_maxit iterations at some step (or met a non-finite state): the whole rollout of that instance
-    // again on the existing kernels, over the device-side list, from the controller's copies of A and B
-    rc = launch_hand_back(h, pl, p, lqmpc::MODE_ROLLOUT, nullptr);
-    if (rc) return rc;
-    h->last_kernel = c->roll_name.c_str();
-    return 0;
+    // (a handed-back instance runs its whole rollout again)
+    return ctl_run(c, pl, p, lqmpc::MODE_ROLLOUT, false, c->roll_name);
 }
 
 int lqmpc_controller_rollout(lqmpc_controller *c, int T, const double *x0, const double *A_true, const double *B_true,
@@ -1447,19 +1328,15 @@ int lqmpc_controller_rollout(lqmpc_controller *c, int T, const double *x0, const
     HIP_TRY(hipSetDevice(h->device));
     Stager s{h};
     const size_t b = (size_t)c->Bsz, nx = (size_t)c->nx, nu = (size_t)c->nu;
-    s.begin(b * 8 * (nx * nx + nx * nu + nx + 2 + (X ? nx * (size_t)(T + 1) : 0) + (U ? nu * (size_t)T : 0)));
-    const double *dx0 = s.in(x0, b * nx);
-    const double *dAt = A_true, *dBt = B_true;
-    if (true_per_instance) { dAt = s.in(A_true, b * nx * nx); dBt = s.in(B_true, b * nx * nu); }
-    double *dJT = s.out(JT, b), *dX = s.out(X, b * nx * (size_t)(T + 1)), *dU = s.out(U, b * nu * (size_t)T);
-    int32_t *dst = s.out(status, b), *dit = s.out(iters, b);
-    s.upload();
-    if (s.rc) return s.rc;
-    int rc = lqmpc_controller_rollout_dev(c, T, dx0, dAt, dBt, true_per_instance, dJT, dX, dU, dst, dit);
-    if (rc) return rc;
-    s.back(JT, dJT, b); s.back(X, dX, b * nx * (size_t)(T + 1)); s.back(U, dU, b * nu * (size_t)T);
-    s.back(status, dst, b); s.back(iters, dit, b);
-    return s.finish();
+    const double *dx0, *dAt = A_true, *dBt = B_true;
+    double *dJT, *dX, *dU;
+    int32_t *dst, *dit;
+    s.in(x0, b * nx, dx0);
+    if (true_per_instance) { s.in(A_true, b * nx * nx, dAt); s.in(B_true, b * nx * nu, dBt); }
+    s.out(JT, b, dJT); s.out(X, b * nx * (size_t)(T + 1), dX); s.out(U, b * nu * (size_t)T, dU); s.out(status, b, dst); s.out(iters, b, dit);
+    int rc = s.upload();
+    if (!rc) rc = lqmpc_controller_rollout_dev(c, T, dx0, dAt, dBt, true_per_instance, dJT, dX, dU, dst, dit);
+    return rc ? rc : s.finish();
 }
 
 int lqmpc_controller_reset(lqmpc_controller *c)
@@ -1467,8 +1344,7 @@ int lqmpc_controller_reset(lqmpc_controller *c)
     if (!c) return fail(LQMPC_ERR_BAD_ARG, "controller is NULL");
     if (!c->face) return 0;
     HIP_TRY(hipSetDevice(c->h->device));
-    const size_t words = c->wg ? (size_t)(lqmpc::WG_CTL_FACE_WORDS + 2 * c->nx) : (size_t)(2 + 2 * c->nx);
-    HIP_TRY(hipMemsetAsync(c->face, 0, (size_t)c->Bsz * words * sizeof(unsigned long long), c->h->stream));
+    HIP_TRY(hipMemsetAsync(c->face, 0, (size_t)c->Bsz * ctl_sizes(c).face_words * sizeof(unsigned long long), c->h->stream));
     return 0;
 }
 
@@ -1487,9 +1363,8 @@ int lqmpc_controller_set_reference(lqmpc_controller *c, const double *x_ref, con
     // on the stream), then one launch rewrites v_r in place -- behind every step enqueued so far, in front of every later one.
     KParams p;
     Plan pl;
-    int rc = prepare(h, c->opt, ctl_call(c), p, pl);
+    int rc = ctl_prepare(c, ctl_call(c), p, pl);
     if (rc) return rc;
-    ctl_bind(c, p);
     if (!(c->wg ? lqmpc::launch_wg_ctl_retarget(p, h->stream) : lqmpc::launch_ctl_retarget(p, h->stream)))
         return fail(LQMPC_ERR_HIP, "controller retarget kernel launch failed");
     HIP_TRY(hipGetLastError());
@@ -1514,7 +1389,7 @@ int lqmpc_controller_set_model_dev(lqmpc_controller *c, int64_t count, const int
     // block holds the references last given by set_reference: v_r of the rewritten records is computed from those.
     KParams p;
     Plan pl;
-    int rc = c->fast ? prepare(h, c->opt, ctl_call(c), p, pl) : 0;
+    int rc = c->fast ? ctl_prepare(c, ctl_call(c), p, pl) : 0;
     if (rc) return rc;
     if (c->A) {
         // (a workgroup-record controller keeps no copies: its records hold A and B)
@@ -1527,7 +1402,6 @@ int lqmpc_controller_set_model_dev(lqmpc_controller *c, int64_t count, const int
         HIP_TRY(hipGetLastError());
     }
     if (!c->fast) return 0;
-    ctl_bind(c, p);
     p.A = dA; p.B = dB; p.Bsz = count;
     p.ctl_idx = didx;
     p.mode = lqmpc::MODE_CTL_FACTOR;
@@ -1554,12 +1428,11 @@ int lqmpc_controller_set_model(lqmpc_controller *c, int64_t count, const int32_t
     HIP_TRY(hipSetDevice(h->device));
     Stager s{h};
     const size_t m = (size_t)count, nx = (size_t)c->nx, nu = (size_t)c->nu;
-    s.begin(m * (8 * (nx * nx + nx * nu) + 4));
-    const int32_t *didx = s.in(idx, m);
-    const double *dA = s.in(A, m * nx * nx), *dB = s.in(B, m * nx * nu);
-    s.upload();
-    if (s.rc) return s.rc;
-    int rc = lqmpc_controller_set_model_dev(c, count, didx, dA, dB);
+    const int32_t *didx;
+    const double *dA, *dB;
+    s.in(idx, m, didx); s.in(A, m * nx * nx, dA); s.in(B, m * nx * nu, dB);
+    int rc = s.upload();
+    if (!rc) rc = lqmpc_controller_set_model_dev(c, count, didx, dA, dB);
     if (rc) return rc;
     // the staging is the handle's and the caller may overwrite A, B and idx as soon as this returns: wait, as create does
     return s.finish();
@@ -1574,7 +1447,7 @@ int lqmpc_controller_destroy(lqmpc_controller *c)
     if (!c) return 0;
     (void)hipSetDevice(c->h->device);
     (void)hipStreamSynchronize(c->h->stream);
-    if (c->h->last_kernel == c->name.c_str() || c->h->last_kernel == c->roll_name.c_str()) c->h->last_kernel = "none";
+    if (c->h->last_owner == c->id) set_last_kernel(c->h, "none");
     ctl_free(c);
     return 0;
 }
