@@ -199,6 +199,32 @@ int lqmpc_solve_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
                           const double *dx0, const double *x_ref, const double *u_ref,
                           double *du0, double *dVN, int32_t *dstatus, int32_t *diters);
 
+/* ---- the same solve, returning the whole optimal plan: the reference's decision variable LQ_MPC_Controller.u (utils_class.py:46),
+ *      read there as controller.u.value after solve ----
+ * Instance-minor, as the rollout's U / X:
+ *     Uplan[(k*N + i)*Bsz + b]     = u_i[k]   i = 0..N-1   the optimal input sequence
+ *     Xplan[(a*(N+1) + i)*Bsz + b] = x_i[a]   i = 0..N     x_0 the given state, x_{i+1} = A x_i + B u_i on the MODEL
+ * Uplan is required (NULL: LQMPC_ERR_BAD_ARG before anything is enqueued); Xplan, status, iters may be NULL; VN stays required.
+ * Contract: u0, VN, status, iters are bit for bit what lqmpc_solve_batch[_dev] returns for the same handle, options and data;
+ * Uplan[:, 0, :] is bit for bit u0; Xplan[:, 0, :] is bit for bit x0; every entry of Uplan lies in [lb, ub] (the 16-lane-row and
+ * workgroup kernels form a bound as centre +- half-width, for u0 as well: exactly lb / ub under a symmetric box, lb / ub to the
+ * rounding of that sum, an ulp or two, under any other).  For an instance with
+ * status 2 (non-finite data) the plan rows are unspecified, as u0 is.  Enqueued on the stream like lqmpc_solve_batch[_dev]: _dev
+ * returns at once.  Every kernel family writes the plan where it writes u0, from the solution vector it already holds, and the states
+ * from the roll of the model that gives V_N: no further arithmetic, N nu + (N + 1) nx more doubles stored per instance. */
+int lqmpc_solve_plan_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                           const double *A, const double *B,
+                           const double *Q, const double *R, const double *P,
+                           const double *lb, const double *ub,
+                           const double *x0, const double *x_ref, const double *u_ref,
+                           double *u0, double *VN, double *Uplan, double *Xplan, int32_t *status, int32_t *iters);
+int lqmpc_solve_plan_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                               const double *dA, const double *dB,
+                               const double *Q, const double *R, const double *P,
+                               const double *lb, const double *ub,
+                               const double *dx0, const double *x_ref, const double *u_ref,
+                               double *du0, double *dVN, double *dUplan, double *dXplan, int32_t *dstatus, int32_t *diters);
+
 /* ---- LQ_MPC_Simulator.simulate, batched (utils_class.py:245-285) ----
  * The model (A,B) drives the QP, the plant (A_true,B_true) drives the state.
  * true_per_instance == 0: A_true/B_true are single HOST matrices shared by the batch
@@ -306,6 +332,9 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
  * step: x is nx x Bsz, instance-minor; u0 (nu x Bsz), VN, status, iters as lqmpc_solve_batch returns them; VN, status, iters may be
  *   NULL.  _dev: device pointers, enqueued on the handle's stream, returns at once.  A non-finite state gives status 2 for that
  *   instance and leaves no trace in the controller.  A step sets the handle's lqmpc_last_kernel.
+ * step_plan: a step that also returns the whole plan, laid out and bound by the contract of lqmpc_solve_plan_batch: Uplan required,
+ *   Xplan, VN, status, iters may be NULL; u0, VN, status, iters and the stored active set are bit for bit those of the plain step, and
+ *   Xplan[:, 0, :] is x.  A pass-through controller runs lqmpc_solve_plan_batch_dev.
  * reset: forget the stored active sets (the next step starts cold).  bytes: HBM held by the controller.  kernel: the kernel its
  *   steps launch (contains "ctl"), or for a pass-through controller the kernel its last step ran.  destroy: NULL is fine.
  * set_reference: new references for every later step, x_ref (nx x N) and u_ref (nu x N) HOST, row-major, NULL = zeros -- for a loop
@@ -359,6 +388,10 @@ int lqmpc_controller_create_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t 
                                 const double *x_ref, const double *u_ref, lqmpc_controller **out);
 int lqmpc_controller_step(lqmpc_controller *c, const double *x, double *u0, double *VN, int32_t *status, int32_t *iters);
 int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, int32_t *dstatus, int32_t *diters);
+int lqmpc_controller_step_plan(lqmpc_controller *c, const double *x, double *u0, double *VN, double *Uplan, double *Xplan,
+                               int32_t *status, int32_t *iters);
+int lqmpc_controller_step_plan_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, double *dUplan, double *dXplan,
+                                   int32_t *dstatus, int32_t *diters);
 int lqmpc_controller_rollout(lqmpc_controller *c, int T, const double *x0,
                              const double *A_true, const double *B_true, int true_per_instance,
                              double *JT, double *X, double *U, int32_t *status, int32_t *iters);
@@ -374,6 +407,10 @@ const char *lqmpc_controller_kernel(const lqmpc_controller *c);
 int lqmpc_controller_destroy(lqmpc_controller *c);
 int lqmpc_jit_compile_controller(int nx, int nu, int N, char *log, int log_len);
 int lqmpc_jit_compile_controller_rollout(int nx, int nu, int N, char *log, int log_len);
+/* ... and the kernels lqmpc_solve_plan_batch / lqmpc_controller_step_plan launch on a run-time compiled shape (the plan is written by
+ * kernels of their own, so that the plain calls' kernels hold none of it; otherwise compiled on the first plan call): returns their
+ * number, 2, or 1 on a wide-state shape (no record controller there). */
+int lqmpc_jit_compile_plan(int nx, int nu, int N, char *log, int log_len);
 
 /* ---- timing on the handle's stream (hipEvents), for bench.py's roofline ----
  * begin/end bracket any number of *_dev calls; end waits for the stream and returns the

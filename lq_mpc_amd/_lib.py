@@ -34,6 +34,8 @@ EXPORTS = [
     "lqmpc_controller_set_model", "lqmpc_controller_set_model_dev", "lqmpc_controller_bytes", "lqmpc_controller_kernel", "lqmpc_controller_destroy",
     "lqmpc_jit_compile_controller",
     "lqmpc_controller_rollout", "lqmpc_controller_rollout_dev", "lqmpc_jit_compile_controller_rollout",
+    "lqmpc_solve_plan_batch", "lqmpc_solve_plan_batch_dev", "lqmpc_controller_step_plan", "lqmpc_controller_step_plan_dev",
+    "lqmpc_jit_compile_plan",
 ]
 
 
@@ -91,6 +93,8 @@ def lib():
     solve_args = dims + [P] * 14
     L.lqmpc_solve_batch.argtypes = solve_args
     L.lqmpc_solve_batch_dev.argtypes = solve_args
+    L.lqmpc_solve_plan_batch.argtypes = solve_args + [P] * 2
+    L.lqmpc_solve_plan_batch_dev.argtypes = solve_args + [P] * 2
     roll_args = dims + [ctypes.c_int] + [P] * 10 + [ctypes.c_int] + [P] * 7
     L.lqmpc_rollout_batch.argtypes = roll_args
     L.lqmpc_rollout_batch_dev.argtypes = roll_args
@@ -109,11 +113,14 @@ def lib():
     L.lqmpc_jit_compile.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
     L.lqmpc_jit_compile_bounds.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
     L.lqmpc_jit_compile_controller.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    L.lqmpc_jit_compile_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
     ctl_create_args = dims + [P] * 9 + [ctypes.POINTER(_H)]
     L.lqmpc_controller_create.argtypes = ctl_create_args
     L.lqmpc_controller_create_dev.argtypes = ctl_create_args
     L.lqmpc_controller_step.argtypes = [_H] + [P] * 5
     L.lqmpc_controller_step_dev.argtypes = [_H] + [P] * 5
+    L.lqmpc_controller_step_plan.argtypes = [_H] + [P] * 7
+    L.lqmpc_controller_step_plan_dev.argtypes = [_H] + [P] * 7
     ctl_roll_args = [_H, ctypes.c_int, P, P, P, ctypes.c_int] + [P] * 5
     L.lqmpc_controller_rollout.argtypes = ctl_roll_args
     L.lqmpc_controller_rollout_dev.argtypes = ctl_roll_args
@@ -157,6 +164,16 @@ def jit_compile_controller(nx, nu, N):
     rc = lib().lqmpc_jit_compile_controller(int(nx), int(nu), int(N), log, len(log))
     if rc < 0:
         raise LqmpcError(f"lqmpc_jit_compile_controller({nx},{nu},{N}) -> {rc}: {log.value.decode(errors='replace')}")
+    return rc
+
+
+def jit_compile_plan(nx, nu, N):
+    """The kernels that write the whole plan (solve; step where a record controller serves the shape), compiled (or found in the
+    cache) now; needs no GPU.  Returns their number."""
+    log = ctypes.create_string_buffer(4096)
+    rc = lib().lqmpc_jit_compile_plan(int(nx), int(nu), int(N), log, len(log))
+    if rc < 0:
+        raise LqmpcError(f"lqmpc_jit_compile_plan({nx},{nu},{N}) -> {rc}: {log.value.decode(errors='replace')}")
     return rc
 
 

@@ -626,15 +626,18 @@ static int run(lqmpc_handle *h, const Plan &pl, KParams &p)
     return rc ? rc : launch_hand_back(h, pl, p, p.mode, nullptr);
 }
 
-// lqmpc_solve_batch_dev under explicit options (a prepared controller passes through here under its own snapshot)
+// lqmpc_solve_batch_dev under explicit options (a prepared controller passes through here under its own snapshot).  dUplan, dXplan:
+// the whole plan of lqmpc_solve_plan_batch_dev (null: none).  The hand-back pass copies the parameter block, so an instance the first
+// pass gave up on has its plan rewritten by the second pass, behind the first on the stream.
 static int solve_dev(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, const double *dA, const double *dB, const double *dx0,
-                     double *du0, double *dVN, int32_t *dstatus, int32_t *diters)
+                     double *du0, double *dVN, int32_t *dstatus, int32_t *diters, double *dUplan = nullptr, double *dXplan = nullptr)
 {
     KParams p;
     Plan pl;
     int rc = prepare(h, opt, c, p, pl);
     if (rc) return rc;
     p.A = dA; p.B = dB; p.x0 = dx0; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
+    p.Uplan = dUplan; p.Xplan = dXplan;
     return run(h, pl, p);
 }
 
@@ -681,6 +684,16 @@ int lqmpc_solve_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, c
     if (!h || !dA || !dB || !dx0 || !du0 || !dVN) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
     const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
     return solve_dev(h, h->opt, c, dA, dB, dx0, du0, dVN, dstatus, diters);
+}
+
+int lqmpc_solve_plan_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *dA, const double *dB,
+                               const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                               const double *dx0, const double *x_ref, const double *u_ref, double *du0, double *dVN,
+                               double *dUplan, double *dXplan, int32_t *dstatus, int32_t *diters)
+{
+    if (!h || !dA || !dB || !dx0 || !du0 || !dVN || !dUplan) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
+    return solve_dev(h, h->opt, c, dA, dB, dx0, du0, dVN, dstatus, diters, dUplan, dXplan);
 }
 
 int lqmpc_rollout_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *dA, const double *dB,
@@ -841,6 +854,28 @@ int lqmpc_solve_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const
     s.out(u0, b * nu, du0); s.out(VN, b, dVN); s.out(status, b, dst); s.out(iters, b, dit);
     rc = s.upload();
     if (!rc) rc = lqmpc_solve_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dx0, x_ref, u_ref, du0, dVN, dst, dit);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_solve_plan_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B,
+                           const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                           const double *x0, const double *x_ref, const double *u_ref, double *u0, double *VN,
+                           double *Uplan, double *Xplan, int32_t *status, int32_t *iters)
+{
+    if (!h || !A || !B || !x0 || !u0 || !VN || !Uplan) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    int rc = check_dims(nx, nu, N, Bsz);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)Bsz;
+    const double *dA, *dB, *dx0;
+    double *du0, *dVN, *dUp, *dXp;
+    int32_t *dst, *dit;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(x0, b * nx, dx0);
+    s.out(u0, b * nu, du0); s.out(VN, b, dVN); s.out(Uplan, b * nu * N, dUp); s.out(Xplan, b * nx * (N + 1), dXp);
+    s.out(status, b, dst); s.out(iters, b, dit);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_solve_plan_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dx0, x_ref, u_ref, du0, dVN, dUp, dXp, dst, dit);
     return rc ? rc : s.finish();
 }
 
@@ -1230,16 +1265,20 @@ int lqmpc_controller_create_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t 
     return ctl_create(h, nx, nu, N, Bsz, dA, dB, hipMemcpyDeviceToDevice, Q, R, P, lb, ub, x_ref, u_ref, out);
 }
 
-int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, int32_t *dstatus, int32_t *diters)
+}  // extern "C"
+
+// lqmpc_controller_step_dev, and with dUplan (dXplan may be null) lqmpc_controller_step_plan_dev
+static int ctl_step_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, double *dUplan, double *dXplan, int32_t *dstatus,
+                        int32_t *diters)
 {
-    if (!c || !dx || !du0) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
     lqmpc_handle *h = c->h;
     HIP_TRY(hipSetDevice(h->device));
     const Call cl = ctl_call(c);
     if (!c->fast) {
         // pass-through: the existing solve path, unchanged, on the controller's copies of A and B
         int rc = dVN ? 0 : ctl_vn(c);
-        if (!rc) rc = solve_dev(h, c->opt, cl, (const double *)c->A, (const double *)c->B, dx, du0, dVN ? dVN : (double *)c->vn, dstatus, diters);
+        if (!rc) rc = solve_dev(h, c->opt, cl, (const double *)c->A, (const double *)c->B, dx, du0, dVN ? dVN : (double *)c->vn, dstatus, diters,
+                                dUplan, dXplan);
         if (!rc) c->name = h->last_kernel;
         return rc;
     }
@@ -1248,8 +1287,43 @@ int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0
     int rc = ctl_prepare(c, cl, p, pl);
     if (rc) return rc;
     p.x0 = dx; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
+    p.Uplan = dUplan; p.Xplan = dXplan;
     p.mode = lqmpc::MODE_CTL_STEP;
     return ctl_run(c, pl, p, lqmpc::MODE_SOLVE, !dVN, c->name);
+}
+
+extern "C" {
+
+int lqmpc_controller_step_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, int32_t *dstatus, int32_t *diters)
+{
+    if (!c || !dx || !du0) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    return ctl_step_dev(c, dx, du0, dVN, nullptr, nullptr, dstatus, diters);
+}
+
+int lqmpc_controller_step_plan_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, double *dUplan, double *dXplan,
+                                   int32_t *dstatus, int32_t *diters)
+{
+    if (!c || !dx || !du0 || !dUplan) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    return ctl_step_dev(c, dx, du0, dVN, dUplan, dXplan, dstatus, diters);
+}
+
+int lqmpc_controller_step_plan(lqmpc_controller *c, const double *x, double *u0, double *VN, double *Uplan, double *Xplan, int32_t *status,
+                               int32_t *iters)
+{
+    if (!c || !x || !u0 || !Uplan) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)c->Bsz;
+    const double *dx;
+    double *du0, *dVN, *dUp, *dXp;
+    int32_t *dst, *dit;
+    s.in(x, b * c->nx, dx);
+    s.out(u0, b * c->nu, du0); s.out(VN, b, dVN); s.out(Uplan, b * c->nu * c->N, dUp); s.out(Xplan, b * c->nx * (c->N + 1), dXp);
+    s.out(status, b, dst); s.out(iters, b, dit);
+    int rc = s.upload();
+    if (!rc) rc = lqmpc_controller_step_plan_dev(c, dx, du0, dVN, dUp, dXp, dst, dit);
+    return rc ? rc : s.finish();
 }
 
 int lqmpc_controller_step(lqmpc_controller *c, const double *x, double *u0, double *VN, int32_t *status, int32_t *iters)

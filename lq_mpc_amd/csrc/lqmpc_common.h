@@ -67,6 +67,10 @@ struct KParams {
     const int *ctl_idx;                   // MODE_CTL_FACTOR over an update (lqmpc_controller_set_model): instance j of the launch (A, B, Bsz
                                           // are the update's) writes record ctl_idx[j]; null = record j.  An entry outside [0, ctl_n) is skipped
     long long ctl_n;                      // ... records the controller holds
+    // MODE_SOLVE / MODE_CTL_STEP (lqmpc_solve_plan_batch, lqmpc_controller_step_plan), null in every other call: the whole optimum and
+    // the model's states under it, instance-minor like the rollout's U and X -- Uplan[(k N + i) Bsz + b] = u_i[k], i < N;
+    // Xplan[(a (N + 1) + i) Bsz + b] = x_i[a], i <= N.  Xplan may be null where Uplan is given.  (Last: every field above keeps its offset.)
+    double *Uplan, *Xplan;
 };
 
 // One record of a prepared controller, in doubles: [A | B | G | v_r] (what every step reads) then [W] then [P] (what only the active-set

@@ -25,12 +25,22 @@ __global__ void __launch_bounds__(64, (R16Build<NX, NU, N, LPI>::WAVES)) lqmpc_c
     r16_body<NX, NU, N, MODE, LPI, R16Build<NX, NU, N, LPI>::OCC>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
 }
 
+// MODE_CTL_STEP with the whole plan written out (p.Uplan): a kernel of its own, so that the plain step's kernel holds none of it
+template <int NX, int NU, int N, int LPI>
+__global__ void __launch_bounds__(64, (R16Build<NX, NU, N, LPI>::WAVES)) lqmpc_ctl_plan_kernel(KParams p)
+{
+    using C = R16<NX, NU, N, LPI, (R16Build<NX, NU, N, LPI>::OCC == 2)>;
+    __shared__ double lds_raw[C::IPW * C::INST];
+    r16_body<NX, NU, N, MODE_CTL_STEP, LPI, R16Build<NX, NU, N, LPI>::OCC, false, true>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
+}
+
 template <int NX, int NU, int N, int LPI>
 static void launch_ctl_one(const KParams &p, hipStream_t stream)
 {
     constexpr int IPW = 64 / LPI;
     const dim3 grid((unsigned)((p.Bsz + IPW - 1) / IPW));
-    if (p.mode == MODE_CTL_FACTOR) hipLaunchKernelGGL((lqmpc_ctl_kernel<NX, NU, N, MODE_CTL_FACTOR, LPI>), grid, dim3(64), 0, stream, p);
+    if (p.mode == MODE_CTL_STEP && p.Uplan) hipLaunchKernelGGL((lqmpc_ctl_plan_kernel<NX, NU, N, LPI>), grid, dim3(64), 0, stream, p);
+    else if (p.mode == MODE_CTL_FACTOR) hipLaunchKernelGGL((lqmpc_ctl_kernel<NX, NU, N, MODE_CTL_FACTOR, LPI>), grid, dim3(64), 0, stream, p);
     else if (p.mode == MODE_CTL_ROLL) hipLaunchKernelGGL((lqmpc_ctl_kernel<NX, NU, N, MODE_CTL_ROLL, LPI>), grid, dim3(64), 0, stream, p);
     else hipLaunchKernelGGL((lqmpc_ctl_kernel<NX, NU, N, MODE_CTL_STEP, LPI>), grid, dim3(64), 0, stream, p);
 }

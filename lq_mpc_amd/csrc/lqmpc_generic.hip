@@ -381,7 +381,8 @@ __device__ static inline double u_of(const Ctx &c, int i)
 }
 
 // V_N = cost* + x0'Qx0 by rolling the MODEL forward with the optimal inputs (utils_class.py:62-75, 91)
-__device__ static double value_fn(const Ctx &c)
+// xplan: the states the roll passes go to p.Xplan (lqmpc_solve_plan_batch; null: none), x_0 .. x_N
+__device__ static double value_fn(const Ctx &c, double *xplan = nullptr)
 {
     const KParams &p = c.p; double *ws = c.ws; const long long b = c.b, stride = c.stride, Bsz = p.Bsz;
     const int nx = c.nx, nu = c.nu, N = c.N; const GenOff &o = c.o;
@@ -389,6 +390,7 @@ __device__ static double value_fn(const Ctx &c)
     double cost = 0.0;
     for (int a = 0; a < nx; ++a) for (int d = 0; d < nx; ++d) cost = __builtin_fma(WS(o.x, a) * Q[a * nx + d], WS(o.x, d), cost);
     for (int a = 0; a < nx; ++a) WS(o.xt, a) = WS(o.x, a);
+    if (xplan) for (int a = 0; a < nx; ++a) xplan[(long long)a * (N + 1) * Bsz + b] = WS(o.x, a);
     for (int i = 0; i < N; ++i) {
         const double *Qi = sh + ((i < N - 1) ? p.so.Q : p.so.P);
         for (int a = 0; a < nx; ++a) {
@@ -398,6 +400,7 @@ __device__ static double value_fn(const Ctx &c)
             WS(o.lam, a) = s;
         }
         for (int a = 0; a < nx; ++a) WS(o.xt, a) = WS(o.lam, a);
+        if (xplan) for (int a = 0; a < nx; ++a) xplan[((long long)a * (N + 1) + i + 1) * Bsz + b] = WS(o.xt, a);
         for (int a = 0; a < nx; ++a) WS(o.lam, a) = WS(o.xt, a) - (p.has_ref ? sh[p.so.xref + a * N + i] : 0.0);
         for (int a = 0; a < nx; ++a) for (int d = 0; d < nx; ++d) cost = __builtin_fma(WS(o.lam, a) * Qi[a * nx + d], WS(o.lam, d), cost);
         for (int k = 0; k < nu; ++k)
@@ -442,7 +445,8 @@ __device__ static void generic_instance(const KParams &p, long long b, long long
         for (int a = 0; a < nx; ++a) WS(o.x, a) = p.x0[(long long)a * Bsz + b];
         status = solve_qp(c, &iters);
         for (int k = 0; k < nu; ++k) p.u0[(long long)k * Bsz + b] = u_of(c, k);
-        p.VN[b] = value_fn(c);
+        if (p.Uplan) for (int i = 0; i < c.n; ++i) p.Uplan[((long long)(i % nu) * c.N + i / nu) * Bsz + b] = u_of(c, i);
+        p.VN[b] = value_fn(c, p.Uplan ? p.Xplan : nullptr);
     } else if (p.mode == MODE_MAXVN) {
         double best = -1e308;
         for (int k = 0; k < p.K; ++k) {

@@ -103,6 +103,7 @@ static unsigned long long fnv(const std::string &s, unsigned long long h = 14695
 }
 
 constexpr int JIT_BOUNDS_SMALL = 100, JIT_BOUNDS_BIG = 101;      // cache keys beside the solver's modes
+constexpr int JIT_PLAN = 64;                                     // ... and MODE_SOLVE | JIT_PLAN, MODE_CTL_STEP | JIT_PLAN: the kernels that write the whole plan
 
 // BigT<NX, NU, N, LPI>::INST restated for run-time dimensions
 static int bounds_big_inst(int nx, int nu, int N, int lpi)
@@ -137,6 +138,15 @@ static std::string program_text(int nx, int nu, int N, int mode)
     // registers, waves per SIMD and the packed flag: R16Build, as the prebuilt kernels of lqmpc_r16.hip / lqmpc_ctl.hip
     int lpi = 0;
     jit_r16_shape(nx, nu, N, &lpi, true);
+    if (mode & JIT_PLAN) {
+        snprintf(buf, sizeof buf,
+                 "#include \"lqmpc_r16_body.h\"\nnamespace lqmpc {\nusing B = R16Build<%d, %d, %d, %d>;\n"
+                 "extern \"C\" __global__ void __launch_bounds__(64, (B::WAVES)) lqmpc_jit_kernel(KParams p)\n"
+                 "{\n    using C = R16<%d, %d, %d, %d, (B::OCC == 2)>;\n    __shared__ double lds_raw[C::IPW * C::INST];\n"
+                 "    r16_body<%d, %d, %d, %d, %d, B::OCC, false, true>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);\n}\n}\n",
+                 nx, nu, N, lpi, nx, nu, N, lpi, nx, nu, N, mode & ~JIT_PLAN, lpi);
+        return buf;
+    }
     snprintf(buf, sizeof buf,
              "#include \"lqmpc_r16_body.h\"\nnamespace lqmpc {\nusing B = R16Build<%d, %d, %d, %d>;\n"
              "extern \"C\" __global__ void __launch_bounds__(64, (B::WAVES)) lqmpc_jit_kernel(KParams p)\n"
@@ -224,6 +234,7 @@ static const char *mode_tag(int mode)
     switch (mode) { case MODE_SOLVE: return "solve"; case MODE_ROLLOUT: return "rollout"; case MODE_MAXVN: return "maxvn";
                     case MODE_PROBE: return "probe"; case MODE_CTL_FACTOR: return "controller factor"; case MODE_CTL_STEP: return "controller step";
                     case MODE_CTL_ROLL: return "controller rollout";
+                    case MODE_SOLVE | JIT_PLAN: return "solve with the plan"; case MODE_CTL_STEP | JIT_PLAN: return "controller step with the plan";
                     default: return "sweep"; }
 }
 
@@ -269,7 +280,9 @@ bool jit_available(int device, int nx, int nu, int N, int mode, std::string *why
 bool launch_jit(int device, const KParams &p, hipStream_t stream, const char **name, std::string *why)
 {
     std::string err;
-    const Loaded *l = get_kernel(device, p.nx, p.nu, p.N, p.mode, err);
+    // a solve or a controller's step that writes the whole plan runs the kernel built for it (compiled on first use, or by lqmpc_jit_compile_plan)
+    const bool plan = p.Uplan && (p.mode == MODE_SOLVE || p.mode == MODE_CTL_STEP);
+    const Loaded *l = get_kernel(device, p.nx, p.nu, p.N, plan ? p.mode | JIT_PLAN : p.mode, err);
     if (!l) { if (why) *why = err; return false; }
     unsigned grid, block = 64;
     if (p.mode == MODE_PROBE) { grid = (unsigned)((p.Bsz + PROBE_WG - 1) / PROBE_WG); block = PROBE_WG; }
@@ -369,6 +382,26 @@ int lqmpc_jit_compile_controller(int nx, int nu, int N, char *log, int log_len)
         }
     }
     return 2;
+}
+
+// ... and the kernels that write the whole plan (lqmpc_solve_plan_batch, lqmpc_controller_step_plan): the solve's, and inside the
+// controller's record domain (nx <= 8) the step's; returns their number, 2 or 1.  (An entry point of its own: the counts above are pinned.)
+int lqmpc_jit_compile_plan(int nx, int nu, int N, char *log, int log_len)
+{
+    if (log && log_len > 0) log[0] = '\0';
+    if (!lqmpc::jit_r16_shape(nx, nu, N, nullptr, true)) return LQMPC_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lock(lqmpc::g_mu);
+    int count = 0;
+    for (int mode : {(int)lqmpc::MODE_SOLVE | lqmpc::JIT_PLAN, (int)lqmpc::MODE_CTL_STEP | lqmpc::JIT_PLAN}) {
+        if (mode != ((int)lqmpc::MODE_SOLVE | lqmpc::JIT_PLAN) && !lqmpc::jit_r16_shape(nx, nu, N, nullptr)) continue;
+        std::string err;
+        if (!lqmpc::get_code(nx, nu, N, mode, err)) {
+            if (log && log_len > 0) snprintf(log, (size_t)log_len, "%s: %s", lqmpc::mode_tag(mode), err.c_str());
+            return LQMPC_ERR_UNSUPPORTED;
+        }
+        ++count;
+    }
+    return count;
 }
 
 // ... and the rollout kernel of a prepared controller (MODE_CTL_ROLL); returns 1.  (An entry point of its own: the count above is pinned.)

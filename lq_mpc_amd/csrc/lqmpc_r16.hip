@@ -35,12 +35,22 @@ __global__ void __launch_bounds__(64, (R16Build<NX, NU, N, LPI>::WAVES)) lqmpc_r
     r16_body<NX, NU, N, MODE, LPI, R16Build<NX, NU, N, LPI>::OCC, (MODE == MODE_ROLLOUT && R16Build<NX, NU, N, LPI>::CHUNKS)>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
 }
 
+// MODE_SOLVE with the whole plan written out (p.Uplan): a kernel of its own, so that lqmpc_r16_kernel<.., MODE_SOLVE, ..> holds none of it
+template <int NX, int NU, int N, int LPI>
+__global__ void __launch_bounds__(64, (R16Build<NX, NU, N, LPI>::WAVES)) lqmpc_r16_plan_kernel(KParams p)
+{
+    using C = R16<NX, NU, N, LPI, (R16Build<NX, NU, N, LPI>::OCC == 2)>;
+    __shared__ double lds_raw[C::IPW * C::INST];
+    r16_body<NX, NU, N, MODE_SOLVE, LPI, R16Build<NX, NU, N, LPI>::OCC, false, true>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
+}
+
 template <int NX, int NU, int N, int LPI>
 static void launch_r16_one(const KParams &p, hipStream_t stream)
 {
     constexpr int IPW = 64 / LPI;
     const dim3 grid((unsigned)((p.Bsz + IPW - 1) / IPW));
-    if (p.mode == MODE_SOLVE) hipLaunchKernelGGL((lqmpc_r16_kernel<NX, NU, N, MODE_SOLVE, LPI>), grid, dim3(64), 0, stream, p);
+    if (p.mode == MODE_SOLVE && p.Uplan) hipLaunchKernelGGL((lqmpc_r16_plan_kernel<NX, NU, N, LPI>), grid, dim3(64), 0, stream, p);
+    else if (p.mode == MODE_SOLVE) hipLaunchKernelGGL((lqmpc_r16_kernel<NX, NU, N, MODE_SOLVE, LPI>), grid, dim3(64), 0, stream, p);
     else if (p.mode == MODE_MAXVN) hipLaunchKernelGGL((lqmpc_r16_kernel<NX, NU, N, MODE_MAXVN, LPI>), grid, dim3(64), 0, stream, p);
     else if (p.mode == MODE_SWEEP) hipLaunchKernelGGL((lqmpc_r16_kernel<NX, NU, N, MODE_SWEEP, LPI>), grid, dim3(64), 0, stream, p);
     else {

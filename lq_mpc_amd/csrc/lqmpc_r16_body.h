@@ -168,7 +168,10 @@ __device__ __forceinline__ unsigned row_umax(unsigned x)
 // and the plant live in LDS instead of registers (they are the loop-invariant values the allocator would otherwise reload
 // from scratch in every step).
 // CHUNKS: the closed loop takes its iteration-free steps in speculative chunks (below, "Iteration-free steps in speculative chunks").
-template <int NX, int NU, int N, int MODE, int LPI = 16, int OCC = 1, bool CHUNKS = false>
+// PLAN (MODE_SOLVE, MODE_CTL_STEP): the instantiation behind lqmpc_solve_plan_batch / lqmpc_controller_step_plan, which also stores
+// the whole plan (p.Uplan, p.Xplan).  A kernel of its own, picked by the host: with PLAN = false nothing of it is compiled in, so
+// the plain calls run the code they ran before the plan existed.
+template <int NX, int NU, int N, int MODE, int LPI = 16, int OCC = 1, bool CHUNKS = false, bool PLAN = false>
 __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long long slot0, long long slot_end)
 {
     constexpr bool PACKED = (OCC == 2);
@@ -1136,6 +1139,20 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
         auto Av = [&](int a, int c) -> double { if constexpr (OCC == 2) return cA[a * NX + c]; else return Am[a][c]; };
         auto Bv = [&](int a, int k) -> double { if constexpr (OCC == 2) return cB[a * NU + k]; else return Bmm[a][k]; };
         auto Pv = [&](int a, int c) -> double { if constexpr (OCC == 2) return cP[a * NX + c]; else return Pm[a][c]; };
+        // The whole plan (PLAN kernels; one QP per call): the inputs are written by the lanes that own their rows (plan_rows), the
+        // model's states from inside value_fn, which rolls through them anyway.  n_x <= 8: every lane of the instance holds the state
+        // and its FIRST lane stores all n_x components of a stage -- with four instances a wavefront a store instruction writes four
+        // 8-byte values, with one instance a wavefront (LPI = 64) a single one.  (One component a lane was tried and is not what is
+        // built: the select that picks a lane's component was compiled to an indexed access through scratch.)  Wide states: lane
+        // a < NX owns component a and stores it.
+        static_assert(!PLAN || MODE == MODE_SOLVE || CTL_S, "the plan belongs to one QP per call");
+        const bool xplan = PLAN && p.Xplan && valid && (NX > 8 ? i < NX : i == 0);
+        auto plan_rows = [&](const double (&v)[RB]) {
+#pragma unroll
+            for (int s = 0; s < RB; ++s)
+                if (valid && vrow[s])
+                    p.Uplan[((long long)(rw[s] % NU) * N + rw[s] / NU) * Bsz + bq] = fmin(fmax(v[s], -h[s]), h[s]) + ctr[s];
+        };
         auto value_fn = [&](const double (&x0v)[NX], const double (&v)[RB]) -> double {
             if constexpr (NX > 8) {
                 // wide states: the roll spread over the lanes of the instance like the closed loop below -- lane a < NX owns row a of
@@ -1151,6 +1168,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                     double xm = xs[0], qx = 0.0;
 #pragma unroll
                     for (int a = 1; a < NX; ++a) xm = (i == a) ? xs[a] : xm;
+                    if constexpr (PLAN) { if (xplan) p.Xplan[(long long)i * (N + 1) * Bsz + bq] = xm; }
 #pragma unroll
                     for (int cc = 0; cc < NX; ++cc) qx = __builtin_fma(cQ[ia * NX + cc], xs[cc], qx);
                     cx = xm * qx;
@@ -1172,6 +1190,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                     for (int k = 0; k < NU; ++k) xm = __builtin_fma(rB[k], u[k], xm);
 #pragma unroll
                     for (int a = 0; a < NX; ++a) xs[a] = ibcast<LPI>(xm, a);
+                    if constexpr (PLAN) { if (xplan) p.Xplan[((long long)i * (N + 1) + st + 1) * Bsz + bq] = xm; }
                     double dm = xm;
                     if (p.has_ref) dm -= sh[p.so.xref + ia * N + st];
 #pragma unroll
@@ -1199,6 +1218,12 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
             double xs[NX], c = 0.0;
 #pragma unroll
             for (int a = 0; a < NX; ++a) xs[a] = x0v[a];
+            if constexpr (PLAN) {
+                if (xplan) {
+#pragma unroll
+                    for (int a = 0; a < NX; ++a) p.Xplan[(long long)a * (N + 1) * Bsz + bq] = xs[a];
+                }
+            }
 #pragma unroll
             for (int a = 0; a < NX; ++a)
 #pragma unroll
@@ -1223,7 +1248,11 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                     xn[a] = acc;
                 }
 #pragma unroll
-                for (int a = 0; a < NX; ++a) { xs[a] = xn[a]; if (p.has_ref) xn[a] -= sh[p.so.xref + a * N + st]; }
+                for (int a = 0; a < NX; ++a) {
+                    xs[a] = xn[a];
+                    if constexpr (PLAN) { if (xplan) p.Xplan[((long long)a * (N + 1) + st + 1) * Bsz + bq] = xn[a]; }
+                    if (p.has_ref) xn[a] -= sh[p.so.xref + a * N + st];
+                }
 #pragma unroll
                 for (int a = 0; a < NX; ++a)
 #pragma unroll
@@ -1263,8 +1292,9 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
             }
             qp(x, v);
             double vn = 0.0;
-            if (p.VN) vn = value_fn(x, v);
+            if (p.VN || (PLAN && p.Xplan)) vn = value_fn(x, v);
             stage_input(v, 0, u);
+            if constexpr (PLAN) { if (p.Uplan) plan_rows(v); }
             if (writer) {
                 fc[0] = pL; fc[1] = pU;
 #pragma unroll
@@ -1289,6 +1319,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
             qp(x, v);
             const double vn = value_fn(x, v);
             stage_input(v, 0, u);
+            if constexpr (PLAN) { if (p.Uplan) plan_rows(v); }
             if (writer) {
                 p.VN[b] = vn;
 #pragma unroll

@@ -17,11 +17,21 @@ __global__ void __launch_bounds__(64, 1) lqmpc_r16_lat_kernel(KParams p)
     r16_body<NX, NU, N, MODE, 16, 1>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
 }
 
+// MODE_SOLVE with the whole plan written out (p.Uplan)
+template <int NX, int NU, int N>
+__global__ void __launch_bounds__(64, 1) lqmpc_r16_lat_plan_kernel(KParams p)
+{
+    using C = R16<NX, NU, N, 16, false>;
+    __shared__ double lds_raw[C::IPW * C::INST];
+    r16_body<NX, NU, N, MODE_SOLVE, 16, 1, false, true>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
+}
+
 template <int NX, int NU, int N>
 static void launch_lat_one(const KParams &p, hipStream_t stream)
 {
     const dim3 grid((unsigned)((p.Bsz + 3) / 4));
-    if (p.mode == MODE_SOLVE) hipLaunchKernelGGL((lqmpc_r16_lat_kernel<NX, NU, N, MODE_SOLVE>), grid, dim3(64), 0, stream, p);
+    if (p.mode == MODE_SOLVE && p.Uplan) hipLaunchKernelGGL((lqmpc_r16_lat_plan_kernel<NX, NU, N>), grid, dim3(64), 0, stream, p);
+    else if (p.mode == MODE_SOLVE) hipLaunchKernelGGL((lqmpc_r16_lat_kernel<NX, NU, N, MODE_SOLVE>), grid, dim3(64), 0, stream, p);
     else if (p.mode == MODE_MAXVN) hipLaunchKernelGGL((lqmpc_r16_lat_kernel<NX, NU, N, MODE_MAXVN>), grid, dim3(64), 0, stream, p);
     else if (p.mode == MODE_SWEEP) hipLaunchKernelGGL((lqmpc_r16_lat_kernel<NX, NU, N, MODE_SWEEP>), grid, dim3(64), 0, stream, p);
     else hipLaunchKernelGGL((lqmpc_r16_lat_kernel<NX, NU, N, MODE_ROLLOUT>), grid, dim3(64), 0, stream, p);

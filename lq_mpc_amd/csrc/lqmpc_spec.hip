@@ -732,6 +732,21 @@ struct Spec {
         const double vi = bcast_rt(v[i / LPS], i % LPS);
         return fmin(fmax(vi + 0.5 * (lb + ub), lb), ub);
     }
+    // ... for a run-time index: the register that holds the row is picked by a chain of selects (an indexed access would move v to
+    // scratch), the lane by bcast_rt
+    __device__ __forceinline__ double u_at_rt(const KParams &p, int i) const
+    {
+        const int k = i % NU, jb = i / LPS;
+        const double lb = p.sh[p.so.lb + k], ub = p.sh[p.so.ub + k];
+        double vj = v[0];
+#pragma unroll
+        for (int j = 1; j < RB; ++j) {
+            vj = (jb == j) ? v[j] : vj;
+            asm volatile("" : "+v"(vj));                          // (or the chain is folded back into the indexed access)
+        }
+        const double vi = bcast_rt(vj, i % LPS);
+        return fmin(fmax(vi + 0.5 * (lb + ub), lb), ub);
+    }
 };
 
 // A, B entry of instance b (instance-minor)
@@ -744,7 +759,9 @@ struct Spec {
 #define LDX(e) (p.rec ? p.rec[b * REC + NX * NX + NX * NU + (e)] : LD(p.x0, e))
 
 // One wavefront's work: the SPW instances in slots slot0 .. slot0 + SPW - 1 (slots >= slot_end are surplus).
-template <int NX, int NU, int N, int LPS, int MODE>
+// PLAN (MODE_SOLVE): the instantiation behind lqmpc_solve_plan_batch, which also stores the whole plan; a kernel of its own
+// (lqmpc_spec_plan_kernel, lqmpc_spec_list_plan_kernel), so that the plain call's kernels hold none of it.
+template <int NX, int NU, int N, int LPS, int MODE, bool PLAN = false>
 __device__ __forceinline__ void spec_body(const KParams &p, double *lds, long long slot0, long long slot_end)
 {
     using S = Spec<NX, NU, N, LPS>;
@@ -1033,6 +1050,51 @@ __device__ __forceinline__ void spec_body(const KParams &p, double *lds, long lo
             for (int k = 0; k < NU; ++k) p.u0[(long long)k * Bsz + b] = u0[k];
             p.VN[b] = vn;
         }
+        if constexpr (PLAN) {
+            // The whole plan (lqmpc_solve_plan_batch): the inputs of every stage and the model's states under them, in a pass of its
+            // own over the stages.  value_fn's roll is unrolled over the horizon and keeps every register the kernel has busy; N stages
+            // of stores inside it spilled it (packed C4: no scratch -> 3.3 KB), and a second copy of it on this branch did the same.
+            // This loop is rolled -- the stage index is a run-time value, so the input comes through u_at_rt -- and repeats the
+            // N NX (NX + NU) multiply-adds of the states.
+            double A[NX][NX], Bm[NX][NU], xs[NX];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) {
+                xs[i] = x0[i];
+#pragma unroll
+                for (int j = 0; j < NX; ++j) A[i][j] = LDA(i * NX + j);
+#pragma unroll
+                for (int k = 0; k < NU; ++k) Bm[i][k] = LDB(i * NU + k);
+            }
+            if (writer && p.Xplan) {
+#pragma unroll
+                for (int i = 0; i < NX; ++i) p.Xplan[(long long)i * (N + 1) * Bsz + b] = xs[i];
+            }
+#pragma unroll 1
+            for (int t = 0; t < N; ++t) {
+                double u[NU], xn[NX];
+#pragma unroll
+                for (int k = 0; k < NU; ++k) u[k] = st.u_at_rt(p, t * NU + k);
+#pragma unroll
+                for (int i = 0; i < NX; ++i) {
+                    double acc = 0.0;
+#pragma unroll
+                    for (int j = 0; j < NX; ++j) acc = __builtin_fma(A[i][j], xs[j], acc);
+#pragma unroll
+                    for (int k = 0; k < NU; ++k) acc = __builtin_fma(Bm[i][k], u[k], acc);
+                    xn[i] = acc;
+                }
+#pragma unroll
+                for (int i = 0; i < NX; ++i) xs[i] = xn[i];
+                if (writer) {
+#pragma unroll
+                    for (int k = 0; k < NU; ++k) p.Uplan[((long long)k * N + t) * Bsz + b] = u[k];
+                    if (p.Xplan) {
+#pragma unroll
+                        for (int i = 0; i < NX; ++i) p.Xplan[((long long)i * (N + 1) + t + 1) * Bsz + b] = xn[i];
+                    }
+                }
+            }
+        }
     } else if constexpr (MODE == MODE_MAXVN) {
         double best = -1e308;
         for (int k = 0; k < p.K; ++k) {
@@ -1151,6 +1213,35 @@ __global__ void __launch_bounds__(64, 1) lqmpc_spec_list_kernel(KParams p)
     }
 }
 
+// MODE_SOLVE with the whole plan written out (p.Uplan), on the whole batch and over a device-side list
+template <int NX, int NU, int N, int LPS>
+__global__ void __launch_bounds__(64, 1) lqmpc_spec_plan_kernel(KParams p)
+{
+    using S = Spec<NX, NU, N, LPS>;
+    __shared__ double lds[S::LDS_DOUBLES];
+    long long slot_end = p.Bsz;
+    if (p.count_dev) {
+        const long long cnt = *p.count_dev;
+        slot_end = cnt < slot_end ? cnt : slot_end;
+        if ((long long)blockIdx.x * S::SPW >= slot_end) return;
+    }
+    spec_body<NX, NU, N, LPS, MODE_SOLVE, true>(p, lds, (long long)blockIdx.x * S::SPW, slot_end);
+}
+
+template <int NX, int NU, int N, int LPS>
+__global__ void __launch_bounds__(64, 1) lqmpc_spec_list_plan_kernel(KParams p)
+{
+    using S = Spec<NX, NU, N, LPS>;
+    __shared__ double lds[S::LDS_DOUBLES];
+    const long long cnt = *p.count_dev;
+    const long long slot_end = cnt < p.Bsz ? cnt : p.Bsz;
+#pragma unroll 1
+    for (long long blk = blockIdx.x; blk * S::SPW < slot_end; blk += gridDim.x) {
+        spec_body<NX, NU, N, LPS, MODE_SOLVE, true>(p, lds, blk * S::SPW, slot_end);
+        __syncthreads();
+    }
+}
+
 // Two tiers in one launch (sorted rollouts).  The launch is as long as its slowest wavefront, and in the packed
 // layout that is the wavefront with the instances that stay constrained for all T steps: 16 instances, ~4000
 // instructions per active-set iteration, up to 78 iterations at C3.  So the p.nwide hardest instances, first
@@ -1229,7 +1320,9 @@ static void launch_one(const KParams &p, hipStream_t stream)
     if constexpr (LPS == 64) {
         if (p.count_dev && p.mode != MODE_PROBE) {
             const unsigned gl = grid < 2048u ? grid : 2048u;
-            if (p.mode == MODE_SOLVE)
+            if (p.mode == MODE_SOLVE && p.Uplan)
+                hipLaunchKernelGGL((lqmpc_spec_list_plan_kernel<NX, NU, N, LPS>), dim3(gl), dim3(64), 0, stream, p);
+            else if (p.mode == MODE_SOLVE)
                 hipLaunchKernelGGL((lqmpc_spec_list_kernel<NX, NU, N, LPS, MODE_SOLVE>), dim3(gl), dim3(64), 0, stream, p);
             else if (p.mode == MODE_MAXVN)
                 hipLaunchKernelGGL((lqmpc_spec_list_kernel<NX, NU, N, LPS, MODE_MAXVN>), dim3(gl), dim3(64), 0, stream, p);
@@ -1238,7 +1331,9 @@ static void launch_one(const KParams &p, hipStream_t stream)
             return;
         }
     }
-    if (p.mode == MODE_SOLVE)
+    if (p.mode == MODE_SOLVE && p.Uplan)
+        hipLaunchKernelGGL((lqmpc_spec_plan_kernel<NX, NU, N, LPS>), dim3(grid), dim3(64), 0, stream, p);
+    else if (p.mode == MODE_SOLVE)
         hipLaunchKernelGGL((lqmpc_spec_kernel<NX, NU, N, LPS, MODE_SOLVE>), dim3(grid), dim3(64), 0, stream, p);
     else if (p.mode == MODE_MAXVN)
         hipLaunchKernelGGL((lqmpc_spec_kernel<NX, NU, N, LPS, MODE_MAXVN>), dim3(grid), dim3(64), 0, stream, p);

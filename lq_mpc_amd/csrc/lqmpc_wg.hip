@@ -1053,6 +1053,15 @@ struct Wg {
         }
         return block_sum(c, R);
     }
+    // The whole plan of instance b (lqmpc_solve_plan_batch / lqmpc_controller_step_plan): the inputs as publish_u left them at vw (the
+    // first n of its np rows: the padding rows are not part of the plan), the model's states as the value function's roll left them in Xs.
+    __device__ __forceinline__ void store_plan(long long b) const
+    {
+        const ldsd *uu = lds + o.vw, *Xs = lds + o.Xs;
+        for (int e = t; e < n; e += THREADS) p.Uplan[((long long)(e % nu) * N + e / nu) * p.Bsz + b] = uu[e];
+        if (p.Xplan)
+            for (int e = t; e < nx * (N + 1); e += THREADS) p.Xplan[((long long)(e % nx) * (N + 1) + e / nx) * p.Bsz + b] = Xs[e];
+    }
 };
 
 __global__ void __launch_bounds__(256, 1) lqmpc_wg_kernel(KParams p)
@@ -1282,6 +1291,8 @@ __global__ void __launch_bounds__(256, 1) lqmpc_wg_kernel(KParams p)
         if (p.status) p.status[b] = status;
         if (p.iters) p.iters[b] = iters;
     }
+    // the whole plan of a solve (one QP: vw and Xs are as publish_v and value_fn left them).  Last, so that nothing of it is live above.
+    if (mode == MODE_SOLVE && p.Uplan) w.store_plan(b);
 }
 
 // ---- prepared controller on this kernel's shapes: the set-up once (factor), then one QP per instance and call from its record (step) ----
@@ -1352,10 +1363,11 @@ __global__ void __launch_bounds__(256, 1) lqmpc_wg_ctl_step_kernel(KParams p)
     w.publish_u();
     const ldsd *uu = lds + w.o.vw;
     if (t < nu) p.u0[(long long)t * Bsz + b] = uu[t];
-    if (p.VN) {
+    if (p.VN || p.Xplan) {
         const double vn = w.value_of();
-        if (t == 0) p.VN[b] = vn;
+        if (t == 0 && p.VN) p.VN[b] = vn;
     }
+    if (p.Uplan) w.store_plan(b);
     if (!keep_face) {
         const unsigned long long lo = __ballot(w.own && w.act_prev < 0.0), up = __ballot(w.own && w.act_prev > 0.0);
         if ((t & 63) == 0 && t < 128) { fc[2 * (t >> 6)] = lo; fc[2 * (t >> 6) + 1] = up; }

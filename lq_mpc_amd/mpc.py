@@ -9,6 +9,7 @@ so callers written against the reference (LQ_RDP_Behavior*, mpc_test.py) run unc
 batched entry points a GPU needs (the reference API is one instance per call):
     BatchSolver.solve_batch / rollout_batch / max_vn_batch  over instance-minor (SoA) arrays,
     BatchController(solver, ...).step(x): the set-up kept on the GPU, one QP per instance and call.
+solve_batch and step return the whole optimal plan as well with want_plan=True (the reference's controller.u.value).
 Everything executes in the HIP library behind include/lqmpc.h; there is no CPU path here.
 """
 import ctypes
@@ -168,13 +169,21 @@ class BatchSolver:
             raise ValueError("A must be (nx,nx,Bsz) and B (nx,nu,Bsz), instance-minor")
         return A, B, A.shape[0], B.shape[1], A.shape[2]
 
-    def solve_batch(self, N, A, B, Q, R, P, lb, ub, x0, x_ref=None, u_ref=None):
+    def solve_batch(self, N, A, B, Q, R, P, lb, ub, x0, x_ref=None, u_ref=None, want_plan=False):
+        """want_plan: also "U_plan" (nu, N, Bsz), the whole optimal input sequence, and "X_plan" (nx, N + 1, Bsz), the model's
+        states under it from x0 (lqmpc_solve_plan_batch); the other entries are bit for bit those of the plain call."""
         A, B, nx, nu, Bsz = self._dims(A, B)
         Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
         lb, ub, x0 = _f64(lb, (nu,)), _f64(ub, (nu,)), _f64(x0, (nx, Bsz))
         x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
         u0 = np.empty((nu, Bsz)); VN = np.empty(Bsz)
         status = np.empty(Bsz, dtype=np.int32); iters = np.empty(Bsz, dtype=np.int32)
+        if want_plan:
+            Up = np.empty((nu, N, Bsz)); Xp = np.empty((nx, N + 1, Bsz))
+            _lib.check(self._L.lqmpc_solve_plan_batch(self._h, nx, nu, N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P),
+                                                      _ptr(lb), _ptr(ub), _ptr(x0), _ptr(x_ref), _ptr(u_ref),
+                                                      _ptr(u0), _ptr(VN), _ptr(Up), _ptr(Xp), _ptr(status), _ptr(iters)))
+            return {"u_0": u0, "V_N": VN, "status": status, "iters": iters, "U_plan": Up, "X_plan": Xp}
         _lib.check(self._L.lqmpc_solve_batch(self._h, nx, nu, N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P),
                                              _ptr(lb), _ptr(ub), _ptr(x0), _ptr(x_ref), _ptr(u_ref),
                                              _ptr(u0), _ptr(VN), _ptr(status), _ptr(iters)))
@@ -271,6 +280,15 @@ class BatchSolver:
                                                  _ptr(lb), _ptr(ub), _ptr(dx0), _ptr(x_ref), _ptr(u_ref),
                                                  _ptr(du0), _ptr(dVN), _ptr(dstatus), _ptr(diters)))
 
+    def solve_plan_batch_dev(self, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dx0, du0, dVN, dUplan, dXplan=None, dstatus=None,
+                             diters=None, x_ref=None, u_ref=None):
+        """solve_batch_dev, and the whole plan: dUplan (nu, N, Bsz) required, dXplan (nx, N + 1, Bsz) optional."""
+        Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        _lib.check(self._L.lqmpc_solve_plan_batch_dev(self._h, nx, nu, N, Bsz, _ptr(dA), _ptr(dB), _ptr(Q), _ptr(R), _ptr(P),
+                                                      _ptr(lb), _ptr(ub), _ptr(dx0), _ptr(x_ref), _ptr(u_ref),
+                                                      _ptr(du0), _ptr(dVN), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus), _ptr(diters)))
+
     def rollout_batch_dev(self, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dx0, A_true, B_true, dJT,
                           dX=None, dU=None, dstatus=None, diters=None, true_per_instance=False, x_ref=None, u_ref=None):
         Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
@@ -359,17 +377,28 @@ class BatchController:
             raise _lib.LqmpcError("the controller is closed")
         return self._c
 
-    def step(self, x):
-        """One QP per instance at the states x (nx, Bsz), host arrays in and out."""
+    def step(self, x, want_plan=False):
+        """One QP per instance at the states x (nx, Bsz), host arrays in and out.  want_plan: also "U_plan" (nu, N, Bsz) and
+        "X_plan" (nx, N + 1, Bsz) as BatchSolver.solve_batch returns them (lqmpc_controller_step_plan)."""
         x = _f64(x, (self.nx, self.Bsz))
         u0 = np.empty((self.nu, self.Bsz)); VN = np.empty(self.Bsz)
         status = np.empty(self.Bsz, dtype=np.int32); iters = np.empty(self.Bsz, dtype=np.int32)
+        if want_plan:
+            Up = np.empty((self.nu, self.N, self.Bsz)); Xp = np.empty((self.nx, self.N + 1, self.Bsz))
+            _lib.check(self._L.lqmpc_controller_step_plan(self._live(), _ptr(x), _ptr(u0), _ptr(VN), _ptr(Up), _ptr(Xp),
+                                                          _ptr(status), _ptr(iters)))
+            return {"u_0": u0, "V_N": VN, "status": status, "iters": iters, "U_plan": Up, "X_plan": Xp}
         _lib.check(self._L.lqmpc_controller_step(self._live(), _ptr(x), _ptr(u0), _ptr(VN), _ptr(status), _ptr(iters)))
         return {"u_0": u0, "V_N": VN, "status": status, "iters": iters}
 
     def step_dev(self, dx, du0, dVN=None, dstatus=None, diters=None):
         """Device pointers / tensors; enqueued on the solver's stream, returns at once."""
         _lib.check(self._L.lqmpc_controller_step_dev(self._live(), _ptr(dx), _ptr(du0), _ptr(dVN), _ptr(dstatus), _ptr(diters)))
+
+    def step_plan_dev(self, dx, du0, dUplan, dXplan=None, dVN=None, dstatus=None, diters=None):
+        """step_dev, and the whole plan: dUplan (nu, N, Bsz) required, dXplan (nx, N + 1, Bsz) optional."""
+        _lib.check(self._L.lqmpc_controller_step_plan_dev(self._live(), _ptr(dx), _ptr(du0), _ptr(dVN), _ptr(dUplan), _ptr(dXplan),
+                                                          _ptr(dstatus), _ptr(diters)))
 
     def rollout(self, T, x0, A_true, B_true, want_traj=False):
         """T closed-loop steps of every instance from x0 (nx, Bsz) in one launch, from the controller's present state (its models,
@@ -467,6 +496,13 @@ class BatchController:
             pass
 
 
+class PlanVariable:
+    """Stands where the reference keeps its cp.Variable: `.value` is None before the first solve, then the optimal plan."""
+
+    def __init__(self):
+        self.value = None
+
+
 _default_solver = None
 
 
@@ -491,6 +527,8 @@ class LQ_MPC_Controller:
         self.F_u = np.asarray(F_u, dtype=np.float64)
         self.lb, self.ub = box_from_Fu(self.F_u)
         self._solver = solver
+        # the decision variable of utils_class.py:46: after solve(), u.value is the (nu, N) optimal plan of that call
+        self.u = PlanVariable()
 
     def _s(self):
         return self._solver if self._solver is not None else default_solver()
@@ -500,17 +538,19 @@ class LQ_MPC_Controller:
         nx = self.A.shape[0]
         x0 = np.asarray(x0, dtype=np.float64).reshape(nx, 1)
         out = self._s().solve_batch(self.N, self.A[:, :, None], self.B[:, :, None], self.Q, self.R, self.P,
-                                    self.lb, self.ub, x0, x_ref, u_ref)
+                                    self.lb, self.ub, x0, x_ref, u_ref, want_plan=True)
         self.last_status = int(out["status"][0])
+        self.u.value = out["U_plan"][:, :, 0].copy()
         return {"u_0": out["u_0"][:, 0].copy(), "V_N": float(out["V_N"][0])}
 
     def solve_many(self, x0s, x_ref=None, u_ref=None):
-        """Additive: K initial states of one system in one launch -> {'u_0': (nu,K), 'V_N': (K,)}."""
+        """Additive: K initial states of one system in one launch -> {'u_0': (nu,K), 'V_N': (K,)}; u.value becomes (nu, N, K)."""
         x0s = np.asarray(x0s, dtype=np.float64)
         K = x0s.shape[1]
         A = np.repeat(self.A[:, :, None], K, 2)
         B = np.repeat(self.B[:, :, None], K, 2)
-        out = self._s().solve_batch(self.N, A, B, self.Q, self.R, self.P, self.lb, self.ub, x0s, x_ref, u_ref)
+        out = self._s().solve_batch(self.N, A, B, self.Q, self.R, self.P, self.lb, self.ub, x0s, x_ref, u_ref, want_plan=True)
+        self.u.value = out["U_plan"]
         return {"u_0": out["u_0"], "V_N": out["V_N"], "status": out["status"]}
 
 

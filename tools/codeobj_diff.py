@@ -92,7 +92,10 @@ def compare(label, a_objs, b_objs, out):
                 out.append(f"{label}: {shown}: identical ({len(ta)} instructions" + "".join(f", {k[1:].split('_')[0]} {ra[k]}" for k in RES if k in ra) + ")")
             else:
                 d = sum(1 for ln in difflib.unified_diff(ta, tb, lineterm="", n=0) if ln[:1] in "+-" and ln[:3] not in ("+++", "---"))
-                out.append(f"{label}: {shown}: DIFFERS: {d} diff lines ({len(ta)} -> {len(tb)} instructions)" + ("; " + ", ".join(moved) if moved else ""))
+                # every resource before and after, moved or not (a kernel's own record; device functions left out of line have none)
+                full = [f"{k[1:].split('_')[0]} {ra.get(k)} -> {rb.get(k)}" for k in RES if k in ra or k in rb]
+                out.append(f"{label}: {shown}: DIFFERS: {d} diff lines ({len(ta)} -> {len(tb)} instructions)" + ("; " + ", ".join(moved) if moved else "")
+                           + (" [" + ", ".join(full) + "]" if full else ""))
     return n, same
 
 
