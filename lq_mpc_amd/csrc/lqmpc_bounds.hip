@@ -215,23 +215,51 @@ __device__ double norm2(const Lane &w, int A, int m, int k, int E)
     return sqrt(fmax(emax, 0.0));
 }
 
-// spectral radius of the n x n matrix at X (destroyed; Y is scratch): |M^(2^J)|^(1/2^J) by repeated squaring of the normalised matrix
+// Y = X X (n x n) with every entry a dot product as if accumulated in twice the working precision (Ogita, Rump, Oishi: Dot2 --
+// error-free products by fma, error-free sums, the errors summed apart), so an entry is rounded relative to ITSELF and not to
+// sum |x_il| |x_lj|: for a matrix far from normal the two differ by the cancellation in the product.
+__device__ void square_dot2(const Lane &w, int Y, int X, int n)
+{
+#pragma clang fp contract(off)
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            double s = 0.0, c = 0.0;
+            for (int l = 0; l < n; ++l) {
+                const double a = w(X, i * n + l), b = w(X, l * n + j);
+                const double pr = a * b, pe = __builtin_fma(a, b, -pr);   // a b = pr + pe exactly
+                const double t = s + pr, bb = t - s;
+                const double se = (s - (t - bb)) + (pr - bb);             // s + pr = t + se exactly
+                s = t;
+                c = c + (pe + se);
+            }
+            w(Y, i * n + j) = s + c;
+        }
+}
+
+// spectral radius of the n x n matrix at X (destroyed; Y is scratch): |M^(2^J)|^(1/2^J) by repeated squaring.  As on the chip the
+// iterate is kept in range by powers of two only (Z_{j+1} = (Z_j 2^-e_j)^2 gives log rho = ln 2 sum_j e_j 2^-j + 2^-J log |Z_J| for
+// any integers e_j: no rounding from the normalisation).  The first 16 squarings, whose roundings enter log rho with the largest
+// weights 2^-j and while the transient growth |Z_j| / rho^(2^j) of a matrix far from normal is still there, use square_dot2: with
+// plain products the 9-state integrator chain's closed loop was off by 4e-12 .. 4e-11 depending on the last bits of K.
 __device__ double spectral_radius(const Lane &w, int X, int Y, int n)
 {
-    double lg = 0.0, wgt = 1.0;
+    double acc = 0.0, wgt = 1.0;
     for (int j = 0; j < 56; ++j) {
-        double s = 0.0;
-        for (int e = 0; e < n * n; ++e) s = __builtin_fma(w(X, e), w(X, e), s);
-        s = sqrt(s);
-        if (!(s > 0.0)) return 0.0;                                      // nilpotent
-        lg = __builtin_fma(log(s), wgt, lg);
+        double s2 = 0.0;
+        for (int e = 0; e < n * n; ++e) s2 = __builtin_fma(w(X, e), w(X, e), s2);
+        if (!(s2 > 0.0)) return 0.0;                                     // nilpotent
+        const int ex = __builtin_amdgcn_frexp_exp(s2) >> 1;              // |Z|_F in [2^(ex-1), 2^(ex+1))
+        acc = __builtin_fma(wgt, (double)ex, acc);
         wgt *= 0.5;
-        const double inv = 1.0 / s;
-        for (int e = 0; e < n * n; ++e) w(X, e) *= inv;
-        mm(w, Y, X, false, X, false, n, n, n, false);
+        for (int e = 0; e < n * n; ++e) w(X, e) = __builtin_amdgcn_ldexp(w(X, e), -ex);
+        if (j < 16) square_dot2(w, Y, X, n);
+        else mm(w, Y, X, false, X, false, n, n, n, false);
         const int t = X; X = Y; Y = t;
     }
-    return exp(lg);
+    double s2 = 0.0;
+    for (int e = 0; e < n * n; ++e) s2 = __builtin_fma(w(X, e), w(X, e), s2);
+    if (!(s2 > 0.0)) return 0.0;
+    return exp(__builtin_fma(0.5 * wgt, log(s2), 0.6931471805599453 * acc));
 }
 
 __device__ __forceinline__ double g_x(int power, int i, double eA, double fA)           // utils.py:78-95
@@ -303,6 +331,62 @@ __global__ void __launch_bounds__(64) lqmpc_bounds_kernel(BoundsParams p)
         if (!(hn < 1e300)) { status = 2; break; }
     }
     if (!conv && status == 0) status = 1;
+    // polish: Riccati steps P <- Q + A'P(A - BK(P)).  The doubling inverts H^-1 + G with G = B R^-1 B' explicitly and loses |G| |H| eps
+    // under cheap control; this map never forms G, inverts only R + B'PB and contracts the error of P by rho(A - BK)^2 a step -- fast
+    // exactly where the doubling is inaccurate --, and is neutral elsewhere: 24 steps.  An instance whose doubling broke down starts
+    // over from Q and goes on, up to 256 steps, until it has settled: the step |P+ - P|_F times q / (1 - q), q the contraction seen
+    // between the last two steps -- the error that is left -- is below 1e-14 |P|_F (or the step itself is); it keeps status 2 otherwise.
+    {
+        const bool restart = status == 2;
+        if (restart)
+            for (int e = 0; e < nx * nx; ++e) w(o.Hk, e) = sh[p.oQ + e];
+        double pd = 1.0, pd0 = 1.0, ph = 0.0;
+        bool ok = true, settled = !restart;
+        for (int it = 0; it < 256 && (it < 24 || !settled); ++it) {
+            for (int k = 0; k < nu; ++k)
+                for (int c = 0; c < nx; ++c) {                          // U2 = B'P
+                    double t = 0.0;
+                    for (int a = 0; a < nx; ++a) t = __builtin_fma(Bin(a, k), w(o.Hk, a * nx + c), t);
+                    w(o.U2, k * nx + c) = t;
+                }
+            for (int k = 0; k < nu; ++k)
+                for (int j = 0; j < nu; ++j) {                          // U1 = R + B'PB
+                    double t = sh[p.oR + k * nu + j];
+                    for (int a = 0; a < nx; ++a) t = __builtin_fma(w(o.U2, k * nx + a), Bin(a, j), t);
+                    w(o.U1, k * nu + j) = t;
+                }
+            symmetrise(w, o.U1, nu);
+            ok = spd_inverse(w, o.U1, nu) && ok;
+            for (int k = 0; k < nu; ++k)
+                for (int c = 0; c < nx; ++c) {                          // Md (nu x nx; the table A^d B is built later) = B'P A: T1 holds n_x^2 entries, too few for n_u > n_x
+                    double t = 0.0;
+                    for (int a = 0; a < nx; ++a) t = __builtin_fma(w(o.U2, k * nx + a), Ain(a, c), t);
+                    w(o.Md, k * nx + c) = t;
+                }
+            mm(w, o.K, o.U1, false, o.Md, false, nu, nu, nx, false);    // K
+            for (int a = 0; a < nx; ++a)
+                for (int c = 0; c < nx; ++c) {                          // T2 = A - B K
+                    double t = Ain(a, c);
+                    for (int k = 0; k < nu; ++k) t = __builtin_fma(-Bin(a, k), w(o.K, k * nx + c), t);
+                    w(o.T2, a * nx + c) = t;
+                }
+            mm(w, o.T3, o.Hk, false, o.T2, false, nx, nx, nx, false);   // T3 = P (A - B K)
+            pd0 = pd; pd = 0.0; ph = 0.0;
+            for (int i = 0; i < nx; ++i)
+                for (int j = 0; j < nx; ++j) {
+                    double t = sh[p.oQ + i * nx + j];
+                    for (int l = 0; l < nx; ++l) t = __builtin_fma(Ain(l, i), w(o.T3, l * nx + j), t);   // Q + A' T3
+                    const double d = t - w(o.Hk, i * nx + j);
+                    w(o.T4, i * nx + j) = t;
+                    pd = __builtin_fma(d, d, pd); ph = __builtin_fma(t, t, ph);
+                }
+            for (int e = 0; e < nx * nx; ++e) w(o.Hk, e) = w(o.T4, e);
+            symmetrise(w, o.Hk, nx);
+            const double q2 = fmin(pd / pd0, 0.998), q = sqrt(q2);
+            if (restart) settled = ok && ph < 1e300 && (pd <= 1e-28 * ph || pd * q2 <= 1e-28 * ph * (1.0 - q) * (1.0 - q));
+        }
+        if (restart && settled) status = 0;
+    }
     // K = (R + B'PB)^-1 B'PA   (control.dlqr's gain, u = -K x)
     for (int k = 0; k < nu; ++k)
         for (int c = 0; c < nx; ++c) {                                  // U2 = B'P
@@ -319,15 +403,15 @@ __global__ void __launch_bounds__(64) lqmpc_bounds_kernel(BoundsParams p)
     symmetrise(w, o.U1, nu);
     if (!spd_inverse(w, o.U1, nu)) status = 2;
     for (int k = 0; k < nu; ++k)
-        for (int c = 0; c < nx; ++c) {                                  // T1 (nu x nx) = B'P A
+        for (int c = 0; c < nx; ++c) {                                  // Md (nu x nx; the table A^d B is built later) = B'P A: T1 holds n_x^2 entries, too few for n_u > n_x
             double t = 0.0;
             for (int a = 0; a < nx; ++a) t = __builtin_fma(w(o.U2, k * nx + a), Ain(a, c), t);
-            w(o.T1, k * nx + c) = t;
+            w(o.Md, k * nx + c) = t;
         }
     for (int k = 0; k < nu; ++k)
         for (int c = 0; c < nx; ++c) {
             double t = 0.0;
-            for (int j = 0; j < nu; ++j) t = __builtin_fma(w(o.U1, k * nu + j), w(o.T1, j * nx + c), t);
+            for (int j = 0; j < nu; ++j) t = __builtin_fma(w(o.U1, k * nu + j), w(o.Md, j * nx + c), t);
             w(o.K, k * nx + c) = t;
             if (p.K) p.K[(long long)(k * nx + c) * Bsz + b] = t;
         }
@@ -353,6 +437,9 @@ __global__ void __launch_bounds__(64) lqmpc_bounds_kernel(BoundsParams p)
             w(o.T1, a * nx + c) = t;
         }
     const double rho_cl = spectral_radius(w, o.T1, o.T2, nx);
+    // a "converged" H whose gain does not stabilise (an unreachable eigenvalue on the unit circle: H grows until rounding ends the
+    // iteration) is no solution: rho(A - BK) >= 1 to the accuracy rho has
+    if (status == 0 && !(rho_cl < 1.0 - 1e-12)) status = 2;
     const double rho_K = (rho_cl + 0.4) * (rho_cl + 0.4);                // utils.py:358
     const double C_star = (1.0 + rmax * nK * nK / qmin) * fmax(1.0, qmax / qmin * 1.21);   // utils.py:364-368
     const double gamma = C_star / (1.0 - rho_K);

@@ -113,12 +113,21 @@ __device__ __forceinline__ Sq<TX> inv_spd(const Sq<TX> &M, int r, int c)
 // two only -- Z_{j+1} = (Z_j 2^-e_j)^2 gives log rho = ln 2 sum_j e_j 2^-j + 2^-J log |Z_J| for ANY integers e_j -- so an iteration
 // costs an exponent extraction and a few v_ldexp instead of a square root, a logarithm and a division (they were nine tenths of the
 // kernel); a symmetric matrix cannot collapse under squaring (|Z^2|_F >= |Z|_F^2 / sqrt n), so it is rescaled every fourth
-// iteration only.  -1e300 for a nilpotent matrix.
+// iteration only.  The first exponent e_0 is returned apart, as the integer it is: rho = 2^e0 exp(rest), and a power of two in the
+// data moves e0 and leaves every later bit alone (the norms scale exactly).  dead: a nilpotent matrix, rho = 0.
+struct LogRho { double rest; int e0; bool dead; };
+__device__ __forceinline__ double rho_of(const LogRho &l) { return l.dead ? 0.0 : __builtin_amdgcn_ldexp(exp(l.rest), l.e0); }
+// sqrt(rho): e0 = 2 (e0 >> 1) + (e0 & 1), also for a negative e0
+__device__ __forceinline__ double sqrt_rho_of(const LogRho &l)
+{
+    return l.dead ? 0.0 : __builtin_amdgcn_ldexp(exp(0.5 * __builtin_fma(0.6931471805599453, (double)(l.e0 & 1), l.rest)), l.e0 >> 1);
+}
 template <int TX>
-__device__ __forceinline__ double log_rho(Sq<TX> Y, Sq<TX> Yt, bool symmetric, double ones)
+__device__ __forceinline__ LogRho log_rho(Sq<TX> Y, Sq<TX> Yt, bool symmetric, double ones)
 {
     constexpr int J = 56;
     double acc = 0.0, wgt = 1.0;
+    int e0 = 0;
     bool dead = false;
 #pragma unroll 1
     for (int j = 0; j < J; ++j) {
@@ -126,7 +135,7 @@ __device__ __forceinline__ double log_rho(Sq<TX> Y, Sq<TX> Yt, bool symmetric, d
             const double s2 = frob2(Y, ones);
             dead = dead || !(s2 > 0.0);
             const int e = __builtin_amdgcn_frexp_exp(s2) >> 1;       // |Y|_F in [2^(e-1), 2^(e+1))
-            acc = __builtin_fma(wgt, (double)e, acc);
+            if (j == 0) e0 = e; else acc = __builtin_fma(wgt, (double)e, acc);
 #pragma unroll
             for (int a = 0; a < TX; ++a)
 #pragma unroll
@@ -139,7 +148,7 @@ __device__ __forceinline__ double log_rho(Sq<TX> Y, Sq<TX> Yt, bool symmetric, d
     }
     const double s2 = frob2(Y, ones);
     dead = dead || !(s2 > 0.0);
-    return dead ? -1e300 : __builtin_fma(0.5 * wgt, log(dead ? 1.0 : s2), 0.6931471805599453 * acc);
+    return LogRho{__builtin_fma(0.5 * wgt, log(dead ? 1.0 : s2), 0.6931471805599453 * acc), e0, dead};
 }
 
 // ---------------- kernel 1: the n_x x n_x work, four instances per wavefront ----------------
@@ -187,6 +196,7 @@ __device__ __forceinline__ void bounds_small(const BoundsParams &p)
     }
     // ---- dlqr: P_inf by the doubling iteration (lqmpc_bounds.hip has the scalar form; control.dlqr in the reference) ----
     Sq<TX> Ak = A, Akt = At;
+    const Sq<TX> Q0 = H;
     bool conv = false, bad = false;
     int status = 0;
 #pragma unroll 1
@@ -217,21 +227,20 @@ __device__ __forceinline__ void bounds_small(const BoundsParams &p)
         if (__ballot(!(conv || bad)) == 0ull) break;
     }
     if (bad) status = 2; else if (!conv) status = 1;
-    // K = (R + B'PB)^-1 B'PA  (u = -K x)
-    double K[TX], Kt[TX];
-    {
+    // K = (R + B'PB)^-1 B'PA  (u = -K x) for a symmetric P; returns (R + B'PB)^-1
+    auto gain = [&](const Sq<TX> &P, double (&Ko)[TX]) -> double {
         double SB[TX], F[TX];
         double Re = Rp;
 #pragma unroll
         for (int a = 0; a < TX; ++a) {
             double w = 0.0;
 #pragma unroll
-            for (int k = 0; k < TX; ++k) w = mm4(H.t[k][a], Bp[k], w);
+            for (int k = 0; k < TX; ++k) w = mm4(P.t[k][a], Bp[k], w);
             SB[a] = w;
         }
 #pragma unroll
         for (int k = 0; k < TX; ++k) Re = mm4(Bp[k], SB[k], Re);
-        const Sq<TX> SA = mmTN(H, A);
+        const Sq<TX> SA = mmTN(P, A);
 #pragma unroll
         for (int bb = 0; bb < TX; ++bb) {
             double v = 0.0;
@@ -242,7 +251,50 @@ __device__ __forceinline__ void bounds_small(const BoundsParams &p)
         const double R0 = small_inverse<4>(Re, r, c);                 // (R padded with ones: a full 4 x 4 SPD block)
         const double Rm = (r < NU && c < NU) ? R0 : 0.0;
 #pragma unroll
-        for (int bb = 0; bb < TX; ++bb) { K[bb] = mm4(Rm, F[bb]); Kt[bb] = mm4(K[bb], I4); }
+        for (int bb = 0; bb < TX; ++bb) Ko[bb] = mm4(Rm, F[bb]);
+        return Rm;
+    };
+    // ---- polish: Riccati steps P <- Q + A'P(A - BK(P)).  The doubling inverts H^-1 + G with G = B R^-1 B' explicitly and loses
+    // |G| |H| eps under cheap control (1e-5 of K at R = 1e-6 I, NaN at |G| = 1e12); this map never forms G, inverts only R + B'PB and
+    // contracts the error of P by rho(A - BK)^2 a step -- fast exactly where the doubling is inaccurate -- and is neutral elsewhere.
+    // 24 steps for every instance.  An instance whose doubling broke down starts over from Q and goes on, up to 256 steps, until
+    // it has settled: the step |P+ - P|_F times q / (1 - q), q the contraction seen between the last two steps -- the error that is
+    // left -- is below 1e-14 |P|_F (or the step itself is below 1e-14 |P|_F); it keeps status 2 otherwise.  The others wait for it with
+    // their P frozen, so a neighbour cannot change a bit.
+    {
+        if (bad) H = Q0;
+        double pd = 1.0, pd0 = 1.0, ph = 0.0;
+        bool settled = !bad;
+#pragma unroll 1
+        for (int it = 0; it < 256; ++it) {
+            if (it >= 24 && __ballot(!settled) == 0ull) break;
+            double Kp[TX];
+            gain(H, Kp);
+            Sq<TX> Ac;
+#pragma unroll
+            for (int a = 0; a < TX; ++a)
+#pragma unroll
+                for (int bb = 0; bb < TX; ++bb) Ac.t[a][bb] = mm4(-Bt[a], Kp[bb], A.t[a][bb]);
+            const Sq<TX> Hn = symmetrised(mmTN(A, mmTN(H, Ac), Q0), I4);
+            Sq<TX> D;
+#pragma unroll
+            for (int a = 0; a < TX; ++a)
+#pragma unroll
+                for (int bb = 0; bb < TX; ++bb) D.t[a][bb] = Hn.t[a][bb] - H.t[a][bb];
+            const double pdn = frob2(D, ones), phn = frob2(Hn, ones);
+            if (it < 24 || !settled) {
+                H = Hn; pd0 = pd; pd = pdn; ph = phn;
+                const double q2 = fmin(pd / pd0, 0.998), q = sqrt(q2);
+                if (bad) settled = ph < 1e300 && (pd <= 1e-28 * ph || pd * q2 <= 1e-28 * ph * (1.0 - q) * (1.0 - q));
+            }
+        }
+        if (bad && settled) status = 0;
+    }
+    double K[TX], Kt[TX];
+    {
+        const double Rm = gain(H, K);
+#pragma unroll
+        for (int bb = 0; bb < TX; ++bb) Kt[bb] = mm4(K[bb], I4);
         if (!(total4(fabs(Rm), ones) < 1e300)) status = 2;
     }
     if (valid) {
@@ -301,11 +353,14 @@ __device__ __forceinline__ void bounds_small(const BoundsParams &p)
         for (int k = 1; k <= N; ++k) Phi = mmTN(A, mmTN(Phi, A), Id);  // sum_{k=0..N} (A^k)'A^k = I + A'( .. )A
     }
     Sq<1> BB; BB.t[0][0] = BtB;
-    const double nK = exp(0.5 * log_rho(KtK, KtK, true, ones));
-    const double rho_cl = exp(log_rho(Acl, Aclt, false, ones));
-    const double fA = exp(0.5 * log_rho(AtA, AtA, true, ones));
-    const double fB = exp(0.5 * log_rho(BB, BB, true, ones));
-    const double nPhi = exp(0.5 * log_rho(Phi, Phi, true, ones));
+    const double nK = sqrt_rho_of(log_rho(KtK, KtK, true, ones));
+    const double rho_cl = rho_of(log_rho(Acl, Aclt, false, ones));
+    const double fA = sqrt_rho_of(log_rho(AtA, AtA, true, ones));
+    const double fB = sqrt_rho_of(log_rho(BB, BB, true, ones));
+    const double nPhi = sqrt_rho_of(log_rho(Phi, Phi, true, ones));
+    // a "converged" H whose gain does not stabilise (an unreachable eigenvalue on the unit circle: H grows until rounding ends the
+    // iteration) is no solution: rho(A - BK) >= 1 to the accuracy rho has
+    if (status == 0 && !(rho_cl < 1.0 - 1e-12)) status = 2;
     const double qmax = sh[p.osc + 0], qmin = sh[p.osc + 1], rmax = sh[p.osc + 2];
     const double rho_K = (rho_cl + 0.4) * (rho_cl + 0.4);                // utils.py:358
     const double C_star = (1.0 + rmax * nK * nK / qmin) * fmax(1.0, qmax / qmin * 1.21);   // utils.py:364-368
@@ -499,20 +554,32 @@ __device__ __forceinline__ void bounds_big(const BoundsParams &p, double *lds_ra
                 }
             }
         } else {
-            // the table A^d B (row-major (N nx) x nu), stage by stage: lane (a, k) owns entry (a, k)
-            const bool el = i < NX * NU;
-            const int ea = el ? i / NU : 0, ek = el ? i % NU : 0;
-            double Ar[NX];
+            // the table A^d B (row-major (N nx) x nu), stage by stage: the lanes of the instance own the entries (a, k) = i, i + LPI, ..
+            // (n_x n_u can exceed the 16 lanes of an instance: (8, 4, 8) has 32 entries)
+            constexpr int EPL = (NX * NU + LPI - 1) / LPI;
+            double Ar[EPL][NX];
 #pragma unroll
-            for (int cc = 0; cc < NX; ++cc) Ar[cc] = p.A[(long long)(ea * NX + cc) * Bsz + b];
-            if (el) MdL[ea * NU + ek] = p.B[(long long)(ea * NU + ek) * Bsz + b];
+            for (int s = 0; s < EPL; ++s) {
+                const int e = i + LPI * s;
+                const bool el = e < NX * NU;
+                const int ea = el ? e / NU : 0, ek = el ? e % NU : 0;
+#pragma unroll
+                for (int cc = 0; cc < NX; ++cc) Ar[s][cc] = p.A[(long long)(ea * NX + cc) * Bsz + b];
+                if (el) MdL[ea * NU + ek] = p.B[(long long)(ea * NU + ek) * Bsz + b];
+            }
 #pragma unroll 1
             for (int d = 1; d < N; ++d) {
                 __syncthreads();
-                double t = 0.0;
 #pragma unroll
-                for (int cc = 0; cc < NX; ++cc) t = __builtin_fma(Ar[cc], MdL[((d - 1) * NX + cc) * NU + ek], t);
-                if (el) MdL[(d * NX + ea) * NU + ek] = t;
+                for (int s = 0; s < EPL; ++s) {
+                    const int e = i + LPI * s;
+                    const bool el = e < NX * NU;
+                    const int ea = el ? e / NU : 0, ek = el ? e % NU : 0;
+                    double t = 0.0;
+#pragma unroll
+                    for (int cc = 0; cc < NX; ++cc) t = __builtin_fma(Ar[s][cc], MdL[((d - 1) * NX + cc) * NU + ek], t);
+                    if (el) MdL[(d * NX + ea) * NU + ek] = t;
+                }
             }
             __syncthreads();
             // Gamma (the reference's, with a leading zero block row): block (r, c) = M_{r-1-c} for r > c, r = 0..N, c = 0..N-1
