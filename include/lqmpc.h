@@ -225,6 +225,39 @@ int lqmpc_solve_plan_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t B
                                const double *dx0, const double *x_ref, const double *u_ref,
                                double *du0, double *dVN, double *dUplan, double *dXplan, int32_t *dstatus, int32_t *diters);
 
+/* ---- the same solve, and its derivatives with respect to the measured state: the local feedback law and the value gradient ----
+ * The law of a box-constrained MPC is piecewise affine: inside the critical region of x0 it is u_0 = K_0 x0 + k_0.  Instance-minor:
+ *     K0[(k*nx + a)*Bsz + b]              = d u_0[k] / d x0[a]        the gain of the local law (k_0 = u_0 - K_0 x0 is the caller's)
+ *     dVdx[a*Bsz + b]                     = d V_N / d x0[a]           (V_N includes x0'Q x0)
+ *     Kplan[((k*N + i)*nx + a)*Bsz + b]   = d u_i[k] / d x0[a]        the same for the whole plan, i = 0..N-1
+ * K0 and dVdx are required (NULL: LQMPC_ERR_BAD_ARG before anything is enqueued); Kplan, Uplan, Xplan, status, iters may be NULL.
+ * The call is lqmpc_solve_plan_batch_dev followed by one launch of lqmpc_sens_kernel on the same stream (a post-pass: no solver
+ * kernel holds any of it); where Uplan, Xplan or status is NULL the plan call writes to buffers of the handle, grown as needed.
+ * Contract: u0, VN, status, iters, Uplan, Xplan are bit for bit those of lqmpc_solve_plan_batch[_dev] on the same handle, options and
+ * data, and lqmpc_last_kernel names the solve kernel.  The derivatives are those of the FACE THE RETURNED PLAN REPORTS: an entry of
+ * Uplan is on a bound when it equals, bit for bit, lb_k, ub_k, c_k - h_k or c_k + h_k (the forms the plan contract above names; no
+ * tolerance), the inputs on a bound do not move and the others are free.  On that face d Uplan / d x0 is the solution of an
+ * equality-constrained LQ problem, computed by one backward Riccati sweep with a free mask per stage and one forward product, never
+ * from an n x n matrix: rows of Kplan (and K0) that belong to an input on a bound are exactly 0.0, and Kplan[:, 0] is bit for bit K0.
+ * References and the centre of the box enter only k_0, never the gain.  dVdx follows from the envelope theorem by one costate
+ * recursion over Xplan and holds on every face.  At the border of two critical regions (a weakly active bound) the derivative is
+ * one-sided and the call returns that of the face the plan reports.  With options.polish = 0 the plan need not touch its bounds
+ * bit for bit: the gain is then that of the free face.  An instance with status 2 (non-finite data) gets NaN in K0, dVdx and Kplan. */
+int lqmpc_solve_sens_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                           const double *A, const double *B,
+                           const double *Q, const double *R, const double *P,
+                           const double *lb, const double *ub,
+                           const double *x0, const double *x_ref, const double *u_ref,
+                           double *u0, double *VN, double *K0, double *dVdx, double *Kplan, double *Uplan, double *Xplan,
+                           int32_t *status, int32_t *iters);
+int lqmpc_solve_sens_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                               const double *dA, const double *dB,
+                               const double *Q, const double *R, const double *P,
+                               const double *lb, const double *ub,
+                               const double *dx0, const double *x_ref, const double *u_ref,
+                               double *du0, double *dVN, double *dK0, double *ddVdx, double *dKplan, double *dUplan, double *dXplan,
+                               int32_t *dstatus, int32_t *diters);
+
 /* ---- LQ_MPC_Simulator.simulate, batched (utils_class.py:245-285) ----
  * The model (A,B) drives the QP, the plant (A_true,B_true) drives the state.
  * true_per_instance == 0: A_true/B_true are single HOST matrices shared by the batch
@@ -350,6 +383,12 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
  * step_plan: a step that also returns the whole plan, laid out and bound by the contract of lqmpc_solve_plan_batch: Uplan required,
  *   Xplan, VN, status, iters may be NULL; u0, VN, status, iters and the stored active set are bit for bit those of the plain step, and
  *   Xplan[:, 0, :] is x.  A pass-through controller runs lqmpc_solve_plan_batch_dev.
+ * step_sens: a step_plan that also returns the derivatives with respect to x, laid out and bound by the contract of
+ *   lqmpc_solve_sens_batch: K0 and dVdx required, Kplan, Uplan, Xplan, VN, status, iters may be NULL; u0, VN, status, iters, Uplan,
+ *   Xplan and the stored active set are bit for bit those of step_plan, so the next plain step is the same after either.  It is
+ *   lqmpc_controller_step_plan_dev followed by one launch of lqmpc_sens_kernel, which reads the controller's own copies of A and B
+ *   (on workgroup records, which keep none, the heads of the records): record, workgroup and pass-through controllers alike, under
+ *   every set_model and set_reference so far.
  * reset: forget the stored active sets (the next step starts cold).  bytes: HBM held by the controller.  kernel: the kernel its
  *   steps launch (contains "ctl"), or for a pass-through controller the kernel its last step ran.  destroy: NULL is fine.
  * set_reference: new references for every later step, x_ref (nx x N) and u_ref (nu x N) HOST, row-major, NULL = zeros -- for a loop
@@ -407,6 +446,10 @@ int lqmpc_controller_step_plan(lqmpc_controller *c, const double *x, double *u0,
                                int32_t *status, int32_t *iters);
 int lqmpc_controller_step_plan_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, double *dUplan, double *dXplan,
                                    int32_t *dstatus, int32_t *diters);
+int lqmpc_controller_step_sens(lqmpc_controller *c, const double *x, double *u0, double *VN, double *K0, double *dVdx, double *Kplan,
+                               double *Uplan, double *Xplan, int32_t *status, int32_t *iters);
+int lqmpc_controller_step_sens_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, double *dK0, double *ddVdx,
+                                   double *dKplan, double *dUplan, double *dXplan, int32_t *dstatus, int32_t *diters);
 int lqmpc_controller_rollout(lqmpc_controller *c, int T, const double *x0,
                              const double *A_true, const double *B_true, int true_per_instance,
                              double *JT, double *X, double *U, int32_t *status, int32_t *iters);

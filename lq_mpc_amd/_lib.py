@@ -36,6 +36,7 @@ EXPORTS = [
     "lqmpc_controller_rollout", "lqmpc_controller_rollout_dev", "lqmpc_jit_compile_controller_rollout",
     "lqmpc_solve_plan_batch", "lqmpc_solve_plan_batch_dev", "lqmpc_controller_step_plan", "lqmpc_controller_step_plan_dev",
     "lqmpc_jit_compile_plan",
+    "lqmpc_solve_sens_batch", "lqmpc_solve_sens_batch_dev", "lqmpc_controller_step_sens", "lqmpc_controller_step_sens_dev",
 ]
 
 
@@ -95,6 +96,8 @@ def lib():
     L.lqmpc_solve_batch_dev.argtypes = solve_args
     L.lqmpc_solve_plan_batch.argtypes = solve_args + [P] * 2
     L.lqmpc_solve_plan_batch_dev.argtypes = solve_args + [P] * 2
+    L.lqmpc_solve_sens_batch.argtypes = solve_args + [P] * 5
+    L.lqmpc_solve_sens_batch_dev.argtypes = solve_args + [P] * 5
     roll_args = dims + [ctypes.c_int] + [P] * 10 + [ctypes.c_int] + [P] * 7
     L.lqmpc_rollout_batch.argtypes = roll_args
     L.lqmpc_rollout_batch_dev.argtypes = roll_args
@@ -121,6 +124,8 @@ def lib():
     L.lqmpc_controller_step_dev.argtypes = [_H] + [P] * 5
     L.lqmpc_controller_step_plan.argtypes = [_H] + [P] * 7
     L.lqmpc_controller_step_plan_dev.argtypes = [_H] + [P] * 7
+    L.lqmpc_controller_step_sens.argtypes = [_H] + [P] * 10
+    L.lqmpc_controller_step_sens_dev.argtypes = [_H] + [P] * 10
     ctl_roll_args = [_H, ctypes.c_int, P, P, P, ctypes.c_int] + [P] * 5
     L.lqmpc_controller_rollout.argtypes = ctl_roll_args
     L.lqmpc_controller_rollout_dev.argtypes = ctl_roll_args

@@ -53,6 +53,7 @@ struct lqmpc_handle {
     bool hist_ready = false;         // both sets of order counters are zero / being zeroed by the probe launches: no fill needed
     int hist_turn = 0;               // which set the next probe counts into
     DevBuf st2, it2;                 // lqmpc_sweep_batch_dev without a fused kernel: status / iters of the max-V_N pass
+    DevBuf sens_u, sens_x, sens_st;  // lqmpc_*_sens*: the plan, its states and the status where the caller passed NULL
     DevBuf arena;                    // host-flavour staging (Stager): every array of the call in one block
     HostBuf arena_pin;               // ... its pinned image, for the small calls that go up and come back in one copy each
     HostBuf shared_pin[2];           // source of the shared block's upload
@@ -184,7 +185,7 @@ int lqmpc_destroy(lqmpc_handle *h)
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (DevBuf *b : {&h->shared, &h->ws, &h->key, &h->perm, &h->rec, &h->fail, &h->st2, &h->it2, &h->arena}) if (b->p) (void)hipFree(b->p);
+    for (DevBuf *b : {&h->shared, &h->ws, &h->key, &h->perm, &h->rec, &h->fail, &h->st2, &h->it2, &h->sens_u, &h->sens_x, &h->sens_st, &h->arena}) if (b->p) (void)hipFree(b->p);
     for (HostBuf *b : {&h->arena_pin, &h->shared_pin[0], &h->shared_pin[1]}) {
         if (b->p) (void)hipHostFree(b->p);
         if (b->ev) (void)hipEventDestroy(b->ev);
@@ -628,14 +629,17 @@ static int run(lqmpc_handle *h, const Plan &pl, KParams &p)
 
 // lqmpc_solve_batch_dev under explicit options (a prepared controller passes through here under its own snapshot).  dUplan, dXplan:
 // the whole plan of lqmpc_solve_plan_batch_dev (null: none).  The hand-back pass copies the parameter block, so an instance the first
-// pass gave up on has its plan rewritten by the second pass, behind the first on the stream.
+// pass gave up on has its plan rewritten by the second pass, behind the first on the stream.  so: where the call's shared block keeps
+// Q, R, P, the box and the references (for the post-pass of the sens calls).
 static int solve_dev(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, const double *dA, const double *dB, const double *dx0,
-                     double *du0, double *dVN, int32_t *dstatus, int32_t *diters, double *dUplan = nullptr, double *dXplan = nullptr)
+                     double *du0, double *dVN, int32_t *dstatus, int32_t *diters, double *dUplan = nullptr, double *dXplan = nullptr,
+                     lqmpc::SharedOff *so = nullptr)
 {
     KParams p;
     Plan pl;
     int rc = prepare(h, opt, c, p, pl);
     if (rc) return rc;
+    if (so) *so = p.so;
     p.A = dA; p.B = dB; p.x0 = dx0; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
     p.Uplan = dUplan; p.Xplan = dXplan;
     return run(h, pl, p);
@@ -652,6 +656,28 @@ static int rollout_dev(lqmpc_handle *h, const lqmpc_options &opt, const Call &c,
     p.A = dA; p.B = dB; p.x0 = dx0; p.JT = dJT; p.X = dX; p.U = dU; p.status = dstatus; p.iters = diters;
     if (c.true_per_instance) { p.At = A_true; p.Bt = B_true; }
     return run(h, pl, p);
+}
+
+// The sens calls (lqmpc_solve_sens_batch_dev, lqmpc_controller_step_sens_dev): the plan call, then one launch of lqmpc_sens_kernel
+// behind it on the stream.  What the post-pass reads of the plan call's outputs and the caller did not ask for (NULL) goes to buffers
+// of the handle, grown as needed.
+static int sens_buffers(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, double *&dUplan, double *&dXplan, int32_t *&dstatus)
+{
+    const size_t b = (size_t)Bsz;
+    int rc = 0;
+    if (!dUplan) { rc = ensure(h, h->sens_u, b * nu * N * sizeof(double)); dUplan = (double *)h->sens_u.p; }
+    if (!rc && !dXplan) { rc = ensure(h, h->sens_x, b * nx * (N + 1) * sizeof(double)); dXplan = (double *)h->sens_x.p; }
+    if (!rc && !dstatus) { rc = ensure(h, h->sens_st, b * sizeof(int32_t)); dstatus = (int32_t *)h->sens_st.p; }
+    return rc;
+}
+
+// lqmpc_last_kernel keeps the solve kernel's name
+static int sens_launch(lqmpc_handle *h, lqmpc::SensParams &s)
+{
+    s.sh = (const double *)h->shared.p;
+    if (!lqmpc::launch_sens(s, h->stream)) return fail(LQMPC_ERR_HIP, "lqmpc_sens_kernel launch failed");
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 extern "C" {
@@ -694,6 +720,24 @@ int lqmpc_solve_plan_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t B
     if (!h || !dA || !dB || !dx0 || !du0 || !dVN || !dUplan) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
     const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
     return solve_dev(h, h->opt, c, dA, dB, dx0, du0, dVN, dstatus, diters, dUplan, dXplan);
+}
+
+int lqmpc_solve_sens_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *dA, const double *dB,
+                               const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                               const double *dx0, const double *x_ref, const double *u_ref, double *du0, double *dVN,
+                               double *dK0, double *ddVdx, double *dKplan, double *dUplan, double *dXplan, int32_t *dstatus,
+                               int32_t *diters)
+{
+    if (!h || !dA || !dB || !dx0 || !du0 || !dVN || !dK0 || !ddVdx) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    int rc = check_dims(nx, nu, N, Bsz);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    rc = sens_buffers(h, nx, nu, N, Bsz, dUplan, dXplan, dstatus);
+    if (rc) return rc;
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
+    lqmpc::SensParams s{nx, nu, N, Bsz, dA, dB, Bsz, 1, dUplan, dXplan, dstatus, nullptr, {}, dK0, ddVdx, dKplan};
+    rc = solve_dev(h, h->opt, c, dA, dB, dx0, du0, dVN, dstatus, diters, dUplan, dXplan, &s.so);
+    return rc ? rc : sens_launch(h, s);
 }
 
 int lqmpc_rollout_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *dA, const double *dB,
@@ -876,6 +920,30 @@ int lqmpc_solve_plan_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, 
     s.out(status, b, dst); s.out(iters, b, dit);
     rc = s.upload();
     if (!rc) rc = lqmpc_solve_plan_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dx0, x_ref, u_ref, du0, dVN, dUp, dXp, dst, dit);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_solve_sens_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B,
+                           const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                           const double *x0, const double *x_ref, const double *u_ref, double *u0, double *VN,
+                           double *K0, double *dVdx, double *Kplan, double *Uplan, double *Xplan, int32_t *status, int32_t *iters)
+{
+    if (!h || !A || !B || !x0 || !u0 || !VN || !K0 || !dVdx) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    int rc = check_dims(nx, nu, N, Bsz);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)Bsz;
+    const double *dA, *dB, *dx0;
+    double *du0, *dVN, *dK0, *ddV, *dKp, *dUp, *dXp;
+    int32_t *dst, *dit;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(x0, b * nx, dx0);
+    s.out(u0, b * nu, du0); s.out(VN, b, dVN); s.out(K0, b * nu * nx, dK0); s.out(dVdx, b * nx, ddV);
+    s.out(Kplan, b * nu * N * nx, dKp); s.out(Uplan, b * nu * N, dUp); s.out(Xplan, b * nx * (N + 1), dXp);
+    s.out(status, b, dst); s.out(iters, b, dit);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_solve_sens_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dx0, x_ref, u_ref, du0, dVN, dK0, ddV, dKp, dUp, dXp,
+                                             dst, dit);
     return rc ? rc : s.finish();
 }
 
@@ -1269,7 +1337,7 @@ int lqmpc_controller_create_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t 
 
 // lqmpc_controller_step_dev, and with dUplan (dXplan may be null) lqmpc_controller_step_plan_dev
 static int ctl_step_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, double *dUplan, double *dXplan, int32_t *dstatus,
-                        int32_t *diters)
+                        int32_t *diters, lqmpc::SharedOff *so = nullptr)
 {
     lqmpc_handle *h = c->h;
     HIP_TRY(hipSetDevice(h->device));
@@ -1278,7 +1346,7 @@ static int ctl_step_dev(lqmpc_controller *c, const double *dx, double *du0, doub
         // pass-through: the existing solve path, unchanged, on the controller's copies of A and B
         int rc = dVN ? 0 : ctl_vn(c);
         if (!rc) rc = solve_dev(h, c->opt, cl, (const double *)c->A, (const double *)c->B, dx, du0, dVN ? dVN : (double *)c->vn, dstatus, diters,
-                                dUplan, dXplan);
+                                dUplan, dXplan, so);
         if (!rc) c->name = h->last_kernel;
         return rc;
     }
@@ -1286,6 +1354,7 @@ static int ctl_step_dev(lqmpc_controller *c, const double *dx, double *du0, doub
     Plan pl;
     int rc = ctl_prepare(c, cl, p, pl);
     if (rc) return rc;
+    if (so) *so = p.so;
     p.x0 = dx; p.u0 = du0; p.VN = dVN; p.status = dstatus; p.iters = diters;
     p.Uplan = dUplan; p.Xplan = dXplan;
     p.mode = lqmpc::MODE_CTL_STEP;
@@ -1323,6 +1392,46 @@ int lqmpc_controller_step_plan(lqmpc_controller *c, const double *x, double *u0,
     s.out(status, b, dst); s.out(iters, b, dit);
     int rc = s.upload();
     if (!rc) rc = lqmpc_controller_step_plan_dev(c, dx, du0, dVN, dUp, dXp, dst, dit);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_controller_step_sens_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, double *dK0, double *ddVdx,
+                                   double *dKplan, double *dUplan, double *dXplan, int32_t *dstatus, int32_t *diters)
+{
+    if (!c || !dx || !du0 || !dK0 || !ddVdx) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    int rc = sens_buffers(h, c->nx, c->nu, c->N, c->Bsz, dUplan, dXplan, dstatus);
+    if (rc) return rc;
+    // the model of every instance: the controller's instance-minor copies, or (workgroup records keep none) the heads of its records
+    lqmpc::SensParams s{c->nx, c->nu, c->N, c->Bsz, (const double *)c->A, (const double *)c->B, c->Bsz, 1, dUplan, dXplan, dstatus,
+                        nullptr, {}, dK0, ddVdx, dKplan};
+    if (!c->A) {
+        const lqmpc::WgCtlRec L = lqmpc::wg_ctl_rec_layout(c->nx, c->nu, c->N);
+        s.A = (const double *)c->rec + L.oA; s.B = (const double *)c->rec + L.oB;
+        s.sE = 1; s.sI = L.stride;
+    }
+    rc = ctl_step_dev(c, dx, du0, dVN, dUplan, dXplan, dstatus, diters, &s.so);
+    return rc ? rc : sens_launch(h, s);
+}
+
+int lqmpc_controller_step_sens(lqmpc_controller *c, const double *x, double *u0, double *VN, double *K0, double *dVdx, double *Kplan,
+                               double *Uplan, double *Xplan, int32_t *status, int32_t *iters)
+{
+    if (!c || !x || !u0 || !K0 || !dVdx) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)c->Bsz, nx = (size_t)c->nx, nu = (size_t)c->nu, N = (size_t)c->N;
+    const double *dx;
+    double *du0, *dVN, *dK0, *ddV, *dKp, *dUp, *dXp;
+    int32_t *dst, *dit;
+    s.in(x, b * nx, dx);
+    s.out(u0, b * nu, du0); s.out(VN, b, dVN); s.out(K0, b * nu * nx, dK0); s.out(dVdx, b * nx, ddV);
+    s.out(Kplan, b * nu * N * nx, dKp); s.out(Uplan, b * nu * N, dUp); s.out(Xplan, b * nx * (N + 1), dXp);
+    s.out(status, b, dst); s.out(iters, b, dit);
+    int rc = s.upload();
+    if (!rc) rc = lqmpc_controller_step_sens_dev(c, dx, du0, dVN, dK0, ddV, dKp, dUp, dXp, dst, dit);
     return rc ? rc : s.finish();
 }
 

@@ -59,4 +59,19 @@ bool launch_wg_ctl_retarget(const KParams &p, hipStream_t stream);       // wg_c
 void launch_ctl_scatter_model(double *A, double *B, const double *uA, const double *uB, const int *idx, int nx, int nu, long long count,
                               long long Bsz, hipStream_t stream);
 
+// lqmpc_sens.hip: the post-pass of lqmpc_solve_sens_batch / lqmpc_controller_step_sens -- from a plan the solve kernels have written,
+// the gain of the local feedback law on the plan's face and the gradient of V_N.  One kernel for every shape within the build limits.
+struct SensParams {
+    int nx, nu, N;
+    long long Bsz;
+    const double *A, *B;                  // element e (row-major) of instance b at A[e * sE + b * sI]: instance-minor arrays (sE = Bsz, sI = 1)
+    long long sE, sI;                     // or the heads of a workgroup controller's records (sE = 1, sI = the record stride)
+    const double *Uplan, *Xplan;          // the plan call's outputs, instance-minor
+    const int *status;                    // the plan call's status; 2 gives NaN in every output of the instance
+    const double *sh;                     // shared block (device) of the plan call
+    SharedOff so;
+    double *K0, *dVdx, *Kplan;            // outputs, instance-minor; Kplan may be null
+};
+bool launch_sens(const SensParams &p, hipStream_t stream);
+
 }  // namespace lqmpc

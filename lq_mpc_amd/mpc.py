@@ -169,15 +169,27 @@ class BatchSolver:
             raise ValueError("A must be (nx,nx,Bsz) and B (nx,nu,Bsz), instance-minor")
         return A, B, A.shape[0], B.shape[1], A.shape[2]
 
-    def solve_batch(self, N, A, B, Q, R, P, lb, ub, x0, x_ref=None, u_ref=None, want_plan=False):
+    def solve_batch(self, N, A, B, Q, R, P, lb, ub, x0, x_ref=None, u_ref=None, want_plan=False, want_sens=False):
         """want_plan: also "U_plan" (nu, N, Bsz), the whole optimal input sequence, and "X_plan" (nx, N + 1, Bsz), the model's
-        states under it from x0 (lqmpc_solve_plan_batch); the other entries are bit for bit those of the plain call."""
+        states under it from x0 (lqmpc_solve_plan_batch); the other entries are bit for bit those of the plain call.
+        want_sens: the plan keys, and the derivatives with respect to x0 on the face the plan reports (lqmpc_solve_sens_batch):
+        "K_0" (nu, nx, Bsz), the gain of the local law u_0 = K_0 x0 + k_0; "dV_dx" (nx, Bsz); "K_plan" (nu, N, nx, Bsz), the gain of
+        every stage of the plan."""
         A, B, nx, nu, Bsz = self._dims(A, B)
         Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
         lb, ub, x0 = _f64(lb, (nu,)), _f64(ub, (nu,)), _f64(x0, (nx, Bsz))
         x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
         u0 = np.empty((nu, Bsz)); VN = np.empty(Bsz)
         status = np.empty(Bsz, dtype=np.int32); iters = np.empty(Bsz, dtype=np.int32)
+        if want_sens:
+            Up = np.empty((nu, N, Bsz)); Xp = np.empty((nx, N + 1, Bsz))
+            K0 = np.empty((nu, nx, Bsz)); dV = np.empty((nx, Bsz)); Kp = np.empty((nu, N, nx, Bsz))
+            _lib.check(self._L.lqmpc_solve_sens_batch(self._h, nx, nu, N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P),
+                                                      _ptr(lb), _ptr(ub), _ptr(x0), _ptr(x_ref), _ptr(u_ref),
+                                                      _ptr(u0), _ptr(VN), _ptr(K0), _ptr(dV), _ptr(Kp), _ptr(Up), _ptr(Xp),
+                                                      _ptr(status), _ptr(iters)))
+            return {"u_0": u0, "V_N": VN, "status": status, "iters": iters, "U_plan": Up, "X_plan": Xp,
+                    "K_0": K0, "dV_dx": dV, "K_plan": Kp}
         if want_plan:
             Up = np.empty((nu, N, Bsz)); Xp = np.empty((nx, N + 1, Bsz))
             _lib.check(self._L.lqmpc_solve_plan_batch(self._h, nx, nu, N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P),
@@ -289,6 +301,17 @@ class BatchSolver:
                                                       _ptr(lb), _ptr(ub), _ptr(dx0), _ptr(x_ref), _ptr(u_ref),
                                                       _ptr(du0), _ptr(dVN), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus), _ptr(diters)))
 
+    def solve_sens_batch_dev(self, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dx0, du0, dVN, dK0, ddVdx, dKplan=None, dUplan=None,
+                             dXplan=None, dstatus=None, diters=None, x_ref=None, u_ref=None):
+        """solve_plan_batch_dev, and the derivatives with respect to x0: dK0 (nu, nx, Bsz) and ddVdx (nx, Bsz) required, dKplan
+        (nu, N, nx, Bsz) and the plan's arrays optional (lqmpc_solve_sens_batch_dev)."""
+        Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        _lib.check(self._L.lqmpc_solve_sens_batch_dev(self._h, nx, nu, N, Bsz, _ptr(dA), _ptr(dB), _ptr(Q), _ptr(R), _ptr(P),
+                                                      _ptr(lb), _ptr(ub), _ptr(dx0), _ptr(x_ref), _ptr(u_ref),
+                                                      _ptr(du0), _ptr(dVN), _ptr(dK0), _ptr(ddVdx), _ptr(dKplan), _ptr(dUplan),
+                                                      _ptr(dXplan), _ptr(dstatus), _ptr(diters)))
+
     def rollout_batch_dev(self, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dx0, A_true, B_true, dJT,
                           dX=None, dU=None, dstatus=None, diters=None, true_per_instance=False, x_ref=None, u_ref=None):
         Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
@@ -377,12 +400,22 @@ class BatchController:
             raise _lib.LqmpcError("the controller is closed")
         return self._c
 
-    def step(self, x, want_plan=False):
+    def step(self, x, want_plan=False, want_sens=False):
         """One QP per instance at the states x (nx, Bsz), host arrays in and out.  want_plan: also "U_plan" (nu, N, Bsz) and
-        "X_plan" (nx, N + 1, Bsz) as BatchSolver.solve_batch returns them (lqmpc_controller_step_plan)."""
+        "X_plan" (nx, N + 1, Bsz) as BatchSolver.solve_batch returns them (lqmpc_controller_step_plan).  want_sens: the plan keys
+        and "K_0" (nu, nx, Bsz), "dV_dx" (nx, Bsz), "K_plan" (nu, N, nx, Bsz), the derivatives with respect to x
+        (lqmpc_controller_step_sens)."""
         x = _f64(x, (self.nx, self.Bsz))
         u0 = np.empty((self.nu, self.Bsz)); VN = np.empty(self.Bsz)
         status = np.empty(self.Bsz, dtype=np.int32); iters = np.empty(self.Bsz, dtype=np.int32)
+        if want_sens:
+            Up = np.empty((self.nu, self.N, self.Bsz)); Xp = np.empty((self.nx, self.N + 1, self.Bsz))
+            K0 = np.empty((self.nu, self.nx, self.Bsz)); dV = np.empty((self.nx, self.Bsz))
+            Kp = np.empty((self.nu, self.N, self.nx, self.Bsz))
+            _lib.check(self._L.lqmpc_controller_step_sens(self._live(), _ptr(x), _ptr(u0), _ptr(VN), _ptr(K0), _ptr(dV), _ptr(Kp),
+                                                          _ptr(Up), _ptr(Xp), _ptr(status), _ptr(iters)))
+            return {"u_0": u0, "V_N": VN, "status": status, "iters": iters, "U_plan": Up, "X_plan": Xp,
+                    "K_0": K0, "dV_dx": dV, "K_plan": Kp}
         if want_plan:
             Up = np.empty((self.nu, self.N, self.Bsz)); Xp = np.empty((self.nx, self.N + 1, self.Bsz))
             _lib.check(self._L.lqmpc_controller_step_plan(self._live(), _ptr(x), _ptr(u0), _ptr(VN), _ptr(Up), _ptr(Xp),
@@ -399,6 +432,12 @@ class BatchController:
         """step_dev, and the whole plan: dUplan (nu, N, Bsz) required, dXplan (nx, N + 1, Bsz) optional."""
         _lib.check(self._L.lqmpc_controller_step_plan_dev(self._live(), _ptr(dx), _ptr(du0), _ptr(dVN), _ptr(dUplan), _ptr(dXplan),
                                                           _ptr(dstatus), _ptr(diters)))
+
+    def step_sens_dev(self, dx, du0, dK0, ddVdx, dKplan=None, dUplan=None, dXplan=None, dVN=None, dstatus=None, diters=None):
+        """step_plan_dev, and the derivatives with respect to x: dK0 (nu, nx, Bsz) and ddVdx (nx, Bsz) required, dKplan
+        (nu, N, nx, Bsz) and the plan's arrays optional (lqmpc_controller_step_sens_dev)."""
+        _lib.check(self._L.lqmpc_controller_step_sens_dev(self._live(), _ptr(dx), _ptr(du0), _ptr(dVN), _ptr(dK0), _ptr(ddVdx),
+                                                          _ptr(dKplan), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus), _ptr(diters)))
 
     def rollout(self, T, x0, A_true, B_true, want_traj=False):
         """T closed-loop steps of every instance from x0 (nx, Bsz) in one launch, from the controller's present state (its models,
@@ -542,6 +581,18 @@ class LQ_MPC_Controller:
         self.last_status = int(out["status"][0])
         self.u.value = out["U_plan"][:, :, 0].copy()
         return {"u_0": out["u_0"][:, 0].copy(), "V_N": float(out["V_N"][0])}
+
+    def local_law(self, x0, x_ref, u_ref):
+        """Additive: the affine law the controller follows around x0, u_0 = K_0 x + k_0 for x in the critical region of x0.
+        Returns (K_0, k_0) as (nu, nx) and (nu,) arrays; u.value becomes the plan at x0, as after solve()."""
+        nx = self.A.shape[0]
+        x0 = np.asarray(x0, dtype=np.float64).reshape(nx, 1)
+        out = self._s().solve_batch(self.N, self.A[:, :, None], self.B[:, :, None], self.Q, self.R, self.P,
+                                    self.lb, self.ub, x0, x_ref, u_ref, want_sens=True)
+        self.last_status = int(out["status"][0])
+        self.u.value = out["U_plan"][:, :, 0].copy()
+        K0 = out["K_0"][:, :, 0].copy()
+        return K0, out["u_0"][:, 0] - K0 @ x0[:, 0]
 
     def solve_many(self, x0s, x_ref=None, u_ref=None):
         """Additive: K initial states of one system in one launch -> {'u_0': (nu,K), 'V_N': (K,)}; u.value becomes (nu, N, K)."""
