@@ -258,6 +258,39 @@ int lqmpc_solve_sens_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t B
                                double *du0, double *dVN, double *dK0, double *ddVdx, double *dKplan, double *dUplan, double *dXplan,
                                int32_t *dstatus, int32_t *diters);
 
+/* ---- the gradient of a loss on (u_0, V_N) with respect to the model matrices of every instance ----
+ * Given what a plan or sens call wrote (Uplan, Xplan, status; status may be NULL = all 0) and the cotangents gu0 = d loss / d u_0
+ * (nu, Bsz) and gVN = d loss / d V_N (Bsz) (either may be NULL = zero, not both), instance-minor like A and B:
+ *     gA[(a*nx + c)*Bsz + b]  = d loss / d A[a][c] of instance b
+ *     gB[(a*nu + k)*Bsz + b]  = d loss / d B[a][k] of instance b
+ *     gx0[a*Bsz + b]          = d loss / d x0[a]   (optional, NULL is fine; = K_0'gu0 + gVN dV_N/dx0 of lqmpc_solve_sens_batch)
+ * gA and gB are required (NULL, or both cotangents NULL: LQMPC_ERR_BAD_ARG before anything is enqueued).  The call is the post-pass
+ * alone -- one launch of lqmpc_grad_kernel on the handle's stream, no solve: the cotangents are only known at backward time -- so A, B,
+ * the weights, the box and the references must be those of the call that wrote the plan; lqmpc_last_kernel is left naming the solve
+ * kernel.  The gradient is that of the FACE THE PLAN REPORTS, by the rule of lqmpc_solve_sens_batch: an entry of Uplan is on a bound
+ * when it equals, bit for bit, lb_k, ub_k, c_k - h_k or c_k + h_k (no tolerance), the inputs on a bound do not move and the others are
+ * free.  On that face the gradient is the adjoint of an equality-constrained LQ problem: one backward Riccati sweep with a free mask
+ * per stage, one forward roll of N steps, two costate recursions and 2N rank-1 updates, never an n x n matrix.  The gVN part follows
+ * from the envelope theorem and holds on every face.  At the border of two critical regions the gradient is one-sided.  An instance
+ * whose stage-0 inputs all sit on bounds and whose gVN is 0 gets exact 0.0 everywhere; an instance with status 2 gets NaN in gA, gB
+ * and gx0.  A shape whose LDS image would not fit 160 KiB is refused with LQMPC_ERR_UNSUPPORTED (none within the build limits). */
+int lqmpc_model_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                           const double *A, const double *B,
+                           const double *Q, const double *R, const double *P,
+                           const double *lb, const double *ub,
+                           const double *x_ref, const double *u_ref,
+                           const double *Uplan, const double *Xplan, const int32_t *status,
+                           const double *gu0, const double *gVN,
+                           double *gA, double *gB, double *gx0);
+int lqmpc_model_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                               const double *dA, const double *dB,
+                               const double *Q, const double *R, const double *P,
+                               const double *lb, const double *ub,
+                               const double *x_ref, const double *u_ref,
+                               const double *dUplan, const double *dXplan, const int32_t *dstatus,
+                               const double *dgu0, const double *dgVN,
+                               double *dgA, double *dgB, double *dgx0);
+
 /* ---- LQ_MPC_Simulator.simulate, batched (utils_class.py:245-285) ----
  * The model (A,B) drives the QP, the plant (A_true,B_true) drives the state.
  * true_per_instance == 0: A_true/B_true are single HOST matrices shared by the batch
@@ -389,6 +422,9 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
  *   lqmpc_controller_step_plan_dev followed by one launch of lqmpc_sens_kernel, which reads the controller's own copies of A and B
  *   (on workgroup records, which keep none, the heads of the records): record, workgroup and pass-through controllers alike, under
  *   every set_model and set_reference so far.
+ * model_grad: lqmpc_model_grad_batch on the controller's own copies of A and B (on workgroup records the heads of the records) and its
+ *   current references, for a plan one of its steps wrote since the last set_model / set_reference.  Read-only on the controller:
+ *   the next step is bit for bit what it is without the call.
  * reset: forget the stored active sets (the next step starts cold).  bytes: HBM held by the controller.  kernel: the kernel its
  *   steps launch (contains "ctl"), or for a pass-through controller the kernel its last step ran.  destroy: NULL is fine.
  * set_reference: new references for every later step, x_ref (nx x N) and u_ref (nu x N) HOST, row-major, NULL = zeros -- for a loop
@@ -450,6 +486,10 @@ int lqmpc_controller_step_sens(lqmpc_controller *c, const double *x, double *u0,
                                double *Uplan, double *Xplan, int32_t *status, int32_t *iters);
 int lqmpc_controller_step_sens_dev(lqmpc_controller *c, const double *dx, double *du0, double *dVN, double *dK0, double *ddVdx,
                                    double *dKplan, double *dUplan, double *dXplan, int32_t *dstatus, int32_t *diters);
+int lqmpc_controller_model_grad(lqmpc_controller *c, const double *Uplan, const double *Xplan, const int32_t *status,
+                                const double *gu0, const double *gVN, double *gA, double *gB, double *gx0);
+int lqmpc_controller_model_grad_dev(lqmpc_controller *c, const double *dUplan, const double *dXplan, const int32_t *dstatus,
+                                    const double *dgu0, const double *dgVN, double *dgA, double *dgB, double *dgx0);
 int lqmpc_controller_rollout(lqmpc_controller *c, int T, const double *x0,
                              const double *A_true, const double *B_true, int true_per_instance,
                              double *JT, double *X, double *U, int32_t *status, int32_t *iters);

@@ -37,6 +37,7 @@ EXPORTS = [
     "lqmpc_solve_plan_batch", "lqmpc_solve_plan_batch_dev", "lqmpc_controller_step_plan", "lqmpc_controller_step_plan_dev",
     "lqmpc_jit_compile_plan",
     "lqmpc_solve_sens_batch", "lqmpc_solve_sens_batch_dev", "lqmpc_controller_step_sens", "lqmpc_controller_step_sens_dev",
+    "lqmpc_model_grad_batch", "lqmpc_model_grad_batch_dev", "lqmpc_controller_model_grad", "lqmpc_controller_model_grad_dev",
 ]
 
 
@@ -98,6 +99,8 @@ def lib():
     L.lqmpc_solve_plan_batch_dev.argtypes = solve_args + [P] * 2
     L.lqmpc_solve_sens_batch.argtypes = solve_args + [P] * 5
     L.lqmpc_solve_sens_batch_dev.argtypes = solve_args + [P] * 5
+    L.lqmpc_model_grad_batch.argtypes = dims + [P] * 17
+    L.lqmpc_model_grad_batch_dev.argtypes = dims + [P] * 17
     roll_args = dims + [ctypes.c_int] + [P] * 10 + [ctypes.c_int] + [P] * 7
     L.lqmpc_rollout_batch.argtypes = roll_args
     L.lqmpc_rollout_batch_dev.argtypes = roll_args
@@ -126,6 +129,8 @@ def lib():
     L.lqmpc_controller_step_plan_dev.argtypes = [_H] + [P] * 7
     L.lqmpc_controller_step_sens.argtypes = [_H] + [P] * 10
     L.lqmpc_controller_step_sens_dev.argtypes = [_H] + [P] * 10
+    L.lqmpc_controller_model_grad.argtypes = [_H] + [P] * 8
+    L.lqmpc_controller_model_grad_dev.argtypes = [_H] + [P] * 8
     ctl_roll_args = [_H, ctypes.c_int, P, P, P, ctypes.c_int] + [P] * 5
     L.lqmpc_controller_rollout.argtypes = ctl_roll_args
     L.lqmpc_controller_rollout_dev.argtypes = ctl_roll_args

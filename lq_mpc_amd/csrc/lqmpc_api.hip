@@ -375,11 +375,9 @@ static int ensure_order(lqmpc_handle *h, int nx, int nu, size_t B, bool records)
     return rc;
 }
 
-// Check the arguments, plan the call under `opt`, pack the batch-shared data, upload it (skipped when identical to the last upload),
-// size the workspace, fill the kernel parameter block.
-static int prepare(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, KParams &p, Plan &pl)
+// The checks every call makes of its dimensions, weights and box before anything is enqueued.
+static int check_call(const Call &c)
 {
-    h->fail_cleared = false;
     int rc = check_dims(c.nx, c.nu, c.N, c.Bsz);
     if (rc) return rc;
     if (!c.Q || !c.R || !c.P || !c.lb || !c.ub) return fail(LQMPC_ERR_BAD_ARG, "Q, R, P, lb, ub must not be NULL");
@@ -395,9 +393,13 @@ static int prepare(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, KPa
                      (double)LQMPC_MAX_BOX_CENTRE);
             return fail(LQMPC_ERR_BAD_ARG, buf);
         }
-    HIP_TRY(hipSetDevice(h->device));
-    rc = make_plan(opt, c, h->device, pl);
-    if (rc) return rc;
+    return 0;
+}
+
+// Pack the batch-shared data of a call (Kg: the first gain of an order's roll key, or null = zeros) and upload it, skipped when
+// identical to the last upload; `so` takes the offsets.  The block of a post-pass is the block of the solve it follows, bit for bit.
+static int upload_shared(lqmpc_handle *h, const Call &c, const double *Kg, lqmpc::SharedOff &so)
+{
     const int nx = c.nx, nu = c.nu, N = c.N;
     std::vector<double> sh;
     auto put = [&](const double *src, int count) {
@@ -406,22 +408,18 @@ static int prepare(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, KPa
         if (src) memcpy(sh.data() + off, src, sizeof(double) * count);
         return off;
     };
-    memset(&p, 0, sizeof p);
-    p.so.Q = put(c.Q, nx * nx);
-    p.so.R = put(c.R, nu * nu);
-    p.so.P = put(c.P, nx * nx);
-    p.so.lb = put(c.lb, nu);
-    p.so.ub = put(c.ub, nu);
-    p.so.xref = put(c.x_ref, nx * N);
-    p.so.uref = put(c.u_ref, nu * N);
-    p.so.At = put(c.true_per_instance ? nullptr : c.At_sh, nx * nx);
-    p.so.Bt = put(c.true_per_instance ? nullptr : c.Bt_sh, nx * nu);
-    p.so.x0s = put(c.x0s, c.x0s ? nx * c.K : 1);
-    std::vector<double> Kg((size_t)nu * nx, 0.0);
-    const bool roll = pl.order_roll && host_first_gain(nx, nu, N, c.At_sh, c.Bt_sh, c.Q, c.R, c.P, Kg.data());
-    p.so.Kg = put(roll ? Kg.data() : nullptr, nu * nx);
-    p.order_roll = roll ? 1 : 0;
-    rc = ensure(h, h->shared, sh.size() * sizeof(double));
+    so.Q = put(c.Q, nx * nx);
+    so.R = put(c.R, nu * nu);
+    so.P = put(c.P, nx * nx);
+    so.lb = put(c.lb, nu);
+    so.ub = put(c.ub, nu);
+    so.xref = put(c.x_ref, nx * N);
+    so.uref = put(c.u_ref, nu * N);
+    so.At = put(c.true_per_instance ? nullptr : c.At_sh, nx * nx);
+    so.Bt = put(c.true_per_instance ? nullptr : c.Bt_sh, nx * nu);
+    so.x0s = put(c.x0s, c.x0s ? nx * c.K : 1);
+    so.Kg = put(Kg, nu * nx);
+    int rc = ensure(h, h->shared, sh.size() * sizeof(double));
     if (rc) return rc;
     if (sh != h->shared_host) {
         // The device copy may still be read by an earlier launch on this stream: the copy is ordered behind it by the stream.  No
@@ -438,6 +436,26 @@ static int prepare(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, KPa
         hb.ev_valid = true;
         h->shared_host.swap(sh);
     }
+    return 0;
+}
+
+// Check the arguments, plan the call under `opt`, pack the batch-shared data, upload it (skipped when identical to the last upload),
+// size the workspace, fill the kernel parameter block.
+static int prepare(lqmpc_handle *h, const lqmpc_options &opt, const Call &c, KParams &p, Plan &pl)
+{
+    h->fail_cleared = false;
+    int rc = check_call(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    rc = make_plan(opt, c, h->device, pl);
+    if (rc) return rc;
+    const int nx = c.nx, nu = c.nu, N = c.N;
+    memset(&p, 0, sizeof p);
+    std::vector<double> Kg((size_t)nu * nx, 0.0);
+    const bool roll = pl.order_roll && host_first_gain(nx, nu, N, c.At_sh, c.Bt_sh, c.Q, c.R, c.P, Kg.data());
+    rc = upload_shared(h, c, roll ? Kg.data() : nullptr, p.so);
+    if (rc) return rc;
+    p.order_roll = roll ? 1 : 0;
     p.nx = nx; p.nu = nu; p.N = N; p.n = N * nu;
     p.T = c.T; p.K = c.K; p.mode = c.mode;
     p.true_per_instance = c.true_per_instance;
@@ -680,6 +698,39 @@ static int sens_launch(lqmpc_handle *h, lqmpc::SensParams &s)
     return 0;
 }
 
+// The model-gradient calls (lqmpc_model_grad_batch_dev, lqmpc_controller_model_grad_dev): the checks, the shared block of `c` (the one
+// the plan call before it uploaded, so nothing is copied again) and one launch of lqmpc_grad_kernel.  No solve, no plan: nothing is
+// routed or compiled, and lqmpc_last_kernel is left naming the solve kernel.
+static int grad_check(const void *owner, const Call *c, const double *Uplan, const double *Xplan, const double *gu0, const double *gVN,
+                      const double *gA, const double *gB)
+{
+    if (!owner || !Uplan || !Xplan || !gA || !gB) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (!gu0 && !gVN) return fail(LQMPC_ERR_BAD_ARG, "gu0 and gVN are both NULL: there is no cotangent");
+    if (!c) return 0;                                           // (a controller's own data passed these checks when it was made)
+    const int rc = check_call(*c);
+    if (rc) return rc;
+    if (!lqmpc::grad_fits(c->nx, c->nu, c->N)) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "lqmpc_grad_kernel needs %zu bytes of LDS at (%d,%d,%d): over 160 KiB", lqmpc::grad_lds_bytes(c->nx, c->nu, c->N),
+                 c->nx, c->nu, c->N);
+        return fail(LQMPC_ERR_UNSUPPORTED, buf);
+    }
+    return 0;
+}
+
+static int grad_launch(lqmpc_handle *h, const Call &c, lqmpc::GradParams &g)
+{
+    int rc = grad_check(h, &c, g.Uplan, g.Xplan, g.gu0, g.gVN, g.gA, g.gB);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    rc = upload_shared(h, c, nullptr, g.so);
+    if (rc) return rc;
+    g.sh = (const double *)h->shared.p;
+    if (!lqmpc::launch_grad(g, h->stream)) return fail(LQMPC_ERR_HIP, "lqmpc_grad_kernel launch failed");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 extern "C" {
 
 int lqmpc_reserve(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T)
@@ -738,6 +789,17 @@ int lqmpc_solve_sens_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t B
     lqmpc::SensParams s{nx, nu, N, Bsz, dA, dB, Bsz, 1, dUplan, dXplan, dstatus, nullptr, {}, dK0, ddVdx, dKplan};
     rc = solve_dev(h, h->opt, c, dA, dB, dx0, du0, dVN, dstatus, diters, dUplan, dXplan, &s.so);
     return rc ? rc : sens_launch(h, s);
+}
+
+int lqmpc_model_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *dA, const double *dB,
+                               const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                               const double *x_ref, const double *u_ref, const double *dUplan, const double *dXplan,
+                               const int32_t *dstatus, const double *dgu0, const double *dgVN, double *dgA, double *dgB, double *dgx0)
+{
+    if (!h || !dA || !dB) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
+    lqmpc::GradParams g{nx, nu, N, Bsz, dA, dB, Bsz, 1, dUplan, dXplan, dstatus, nullptr, {}, dgu0, dgVN, dgA, dgB, dgx0};
+    return grad_launch(h, c, g);
 }
 
 int lqmpc_rollout_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *dA, const double *dB,
@@ -944,6 +1006,29 @@ int lqmpc_solve_sens_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, 
     rc = s.upload();
     if (!rc) rc = lqmpc_solve_sens_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dx0, x_ref, u_ref, du0, dVN, dK0, ddV, dKp, dUp, dXp,
                                              dst, dit);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_model_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B,
+                           const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                           const double *x_ref, const double *u_ref, const double *Uplan, const double *Xplan, const int32_t *status,
+                           const double *gu0, const double *gVN, double *gA, double *gB, double *gx0)
+{
+    if (!A || !B) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
+    int rc = grad_check(h, &c, Uplan, Xplan, gu0, gVN, gA, gB);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)Bsz;
+    const double *dA, *dB, *dUp, *dXp, *dgu, *dgV;
+    const int32_t *dst;
+    double *dgA, *dgB, *dgx;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(Uplan, b * nu * N, dUp); s.in(Xplan, b * nx * (N + 1), dXp);
+    s.in(status, b, dst); s.in(gu0, b * nu, dgu); s.in(gVN, b, dgV);
+    s.out(gA, b * nx * nx, dgA); s.out(gB, b * nx * nu, dgB); s.out(gx0, b * nx, dgx);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_model_grad_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, x_ref, u_ref, dUp, dXp, dst, dgu, dgV, dgA, dgB, dgx);
     return rc ? rc : s.finish();
 }
 
@@ -1432,6 +1517,42 @@ int lqmpc_controller_step_sens(lqmpc_controller *c, const double *x, double *u0,
     s.out(status, b, dst); s.out(iters, b, dit);
     int rc = s.upload();
     if (!rc) rc = lqmpc_controller_step_sens_dev(c, dx, du0, dVN, dK0, ddV, dKp, dUp, dXp, dst, dit);
+    return rc ? rc : s.finish();
+}
+
+// read-only on the controller: its copies of A and B (on workgroup records the heads of the records) and its current references
+int lqmpc_controller_model_grad_dev(lqmpc_controller *c, const double *dUplan, const double *dXplan, const int32_t *dstatus,
+                                    const double *dgu0, const double *dgVN, double *dgA, double *dgB, double *dgx0)
+{
+    int rc = grad_check(c, nullptr, dUplan, dXplan, dgu0, dgVN, dgA, dgB);
+    if (rc) return rc;
+    lqmpc::GradParams g{c->nx, c->nu, c->N, c->Bsz, (const double *)c->A, (const double *)c->B, c->Bsz, 1, dUplan, dXplan, dstatus,
+                        nullptr, {}, dgu0, dgVN, dgA, dgB, dgx0};
+    if (!c->A) {
+        const lqmpc::WgCtlRec L = lqmpc::wg_ctl_rec_layout(c->nx, c->nu, c->N);
+        g.A = (const double *)c->rec + L.oA; g.B = (const double *)c->rec + L.oB;
+        g.sE = 1; g.sI = L.stride;
+    }
+    return grad_launch(c->h, ctl_call(c), g);
+}
+
+int lqmpc_controller_model_grad(lqmpc_controller *c, const double *Uplan, const double *Xplan, const int32_t *status,
+                                const double *gu0, const double *gVN, double *gA, double *gB, double *gx0)
+{
+    int rc = grad_check(c, nullptr, Uplan, Xplan, gu0, gVN, gA, gB);
+    if (rc) return rc;
+    if (!lqmpc::grad_fits(c->nx, c->nu, c->N)) return fail(LQMPC_ERR_UNSUPPORTED, "lqmpc_grad_kernel: the LDS image of this shape is over 160 KiB");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)c->Bsz, nx = (size_t)c->nx, nu = (size_t)c->nu, N = (size_t)c->N;
+    const double *dUp, *dXp, *dgu, *dgV;
+    const int32_t *dst;
+    double *dgA, *dgB, *dgx;
+    s.in(Uplan, b * nu * N, dUp); s.in(Xplan, b * nx * (N + 1), dXp); s.in(status, b, dst); s.in(gu0, b * nu, dgu); s.in(gVN, b, dgV);
+    s.out(gA, b * nx * nx, dgA); s.out(gB, b * nx * nu, dgB); s.out(gx0, b * nx, dgx);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_controller_model_grad_dev(c, dUp, dXp, dst, dgu, dgV, dgA, dgB, dgx);
     return rc ? rc : s.finish();
 }
 

@@ -74,4 +74,23 @@ struct SensParams {
 };
 bool launch_sens(const SensParams &p, hipStream_t stream);
 
+// lqmpc_grad.hip: the post-pass of lqmpc_model_grad_batch / lqmpc_controller_model_grad -- from a plan the solve kernels have written and
+// the cotangents of u_0 and V_N, the gradient with respect to A and B of every instance on the plan's face.  One kernel for every
+// shape within the build limits; grad_fits says whether its LDS image does (launch_grad refuses, and launches nothing, where not).
+struct GradParams {
+    int nx, nu, N;
+    long long Bsz;
+    const double *A, *B;                  // as SensParams: element e of instance b at A[e * sE + b * sI]
+    long long sE, sI;
+    const double *Uplan, *Xplan;          // what a plan or sens call wrote, instance-minor
+    const int *status;                    // its status (2 gives NaN in every output of the instance); null: all 0
+    const double *sh;                     // shared block (device): Q, R, P, the box and x_ref at the offsets so
+    SharedOff so;
+    const double *gu0, *gVN;              // d loss / d u_0 (nu, Bsz) and d loss / d V_N (Bsz); either may be null = zero
+    double *gA, *gB, *gx0;                // outputs, instance-minor; gx0 may be null
+};
+size_t grad_lds_bytes(int nx, int nu, int N);
+bool grad_fits(int nx, int nu, int N);
+bool launch_grad(const GradParams &p, hipStream_t stream);
+
 }  // namespace lqmpc

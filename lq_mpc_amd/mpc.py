@@ -312,6 +312,34 @@ class BatchSolver:
                                                       _ptr(du0), _ptr(dVN), _ptr(dK0), _ptr(ddVdx), _ptr(dKplan), _ptr(dUplan),
                                                       _ptr(dXplan), _ptr(dstatus), _ptr(diters)))
 
+    def model_grad_batch(self, N, A, B, Q, R, P, lb, ub, U_plan, X_plan, status=None, g_u0=None, g_VN=None, x_ref=None, u_ref=None):
+        """The gradient of a loss on (u_0, V_N) with respect to the model of every instance, on the face the plan reports
+        (lqmpc_model_grad_batch): U_plan (nu, N, Bsz), X_plan (nx, N + 1, Bsz) and status as a want_plan / want_sens call returned
+        them for the same data; g_u0 (nu, Bsz) = d loss / d u_0 and g_VN (Bsz,) = d loss / d V_N, either may be None (zero), not
+        both.  Returns {"g_A": (nx, nx, Bsz), "g_B": (nx, nu, Bsz), "g_x0": (nx, Bsz)}.  The post-pass alone: no solve."""
+        A, B, nx, nu, Bsz = self._dims(A, B)
+        Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
+        lb, ub = _f64(lb, (nu,)), _f64(ub, (nu,))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        U_plan, X_plan = _f64(U_plan, (nu, N, Bsz)), _f64(X_plan, (nx, N + 1, Bsz))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(Bsz)
+        g_u0 = None if g_u0 is None else _f64(g_u0, (nu, Bsz))
+        g_VN = None if g_VN is None else _f64(g_VN, (Bsz,))
+        gA = np.empty((nx, nx, Bsz)); gB = np.empty((nx, nu, Bsz)); gx = np.empty((nx, Bsz))
+        _lib.check(self._L.lqmpc_model_grad_batch(self._h, nx, nu, N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P), _ptr(lb), _ptr(ub),
+                                                  _ptr(x_ref), _ptr(u_ref), _ptr(U_plan), _ptr(X_plan), _ptr(status), _ptr(g_u0),
+                                                  _ptr(g_VN), _ptr(gA), _ptr(gB), _ptr(gx)))
+        return {"g_A": gA, "g_B": gB, "g_x0": gx}
+
+    def model_grad_batch_dev(self, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dUplan, dXplan, dgA, dgB, dstatus=None, dgu0=None, dgVN=None,
+                             dgx0=None, x_ref=None, u_ref=None):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_model_grad_batch_dev)."""
+        Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        _lib.check(self._L.lqmpc_model_grad_batch_dev(self._h, nx, nu, N, Bsz, _ptr(dA), _ptr(dB), _ptr(Q), _ptr(R), _ptr(P), _ptr(lb),
+                                                      _ptr(ub), _ptr(x_ref), _ptr(u_ref), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus),
+                                                      _ptr(dgu0), _ptr(dgVN), _ptr(dgA), _ptr(dgB), _ptr(dgx0)))
+
     def rollout_batch_dev(self, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dx0, A_true, B_true, dJT,
                           dX=None, dU=None, dstatus=None, diters=None, true_per_instance=False, x_ref=None, u_ref=None):
         Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
@@ -394,6 +422,7 @@ class BatchController:
         _lib.check(make(solver._h, nx, nu, self.N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P), _ptr(lb), _ptr(ub),
                         _ptr(x_ref), _ptr(u_ref), ctypes.byref(c)))
         self._c = c
+        self.model_version = 0                  # counts set_model calls: what a gradient taken later checks its plan against
 
     def _live(self):
         if self._c is None or not self._c.value:
@@ -438,6 +467,24 @@ class BatchController:
         (nu, N, nx, Bsz) and the plan's arrays optional (lqmpc_controller_step_sens_dev)."""
         _lib.check(self._L.lqmpc_controller_step_sens_dev(self._live(), _ptr(dx), _ptr(du0), _ptr(dVN), _ptr(dK0), _ptr(ddVdx),
                                                           _ptr(dKplan), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus), _ptr(diters)))
+
+    def model_grad(self, U_plan, X_plan, status=None, g_u0=None, g_VN=None):
+        """BatchSolver.model_grad_batch on the controller's own models and current references, for a plan one of its steps returned
+        (lqmpc_controller_model_grad).  Read-only on the controller."""
+        nx, nu, N, Bsz = self.nx, self.nu, self.N, self.Bsz
+        U_plan, X_plan = _f64(U_plan, (nu, N, Bsz)), _f64(X_plan, (nx, N + 1, Bsz))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(Bsz)
+        g_u0 = None if g_u0 is None else _f64(g_u0, (nu, Bsz))
+        g_VN = None if g_VN is None else _f64(g_VN, (Bsz,))
+        gA = np.empty((nx, nx, Bsz)); gB = np.empty((nx, nu, Bsz)); gx = np.empty((nx, Bsz))
+        _lib.check(self._L.lqmpc_controller_model_grad(self._live(), _ptr(U_plan), _ptr(X_plan), _ptr(status), _ptr(g_u0), _ptr(g_VN),
+                                                       _ptr(gA), _ptr(gB), _ptr(gx)))
+        return {"g_A": gA, "g_B": gB, "g_x0": gx}
+
+    def model_grad_dev(self, dUplan, dXplan, dgA, dgB, dstatus=None, dgu0=None, dgVN=None, dgx0=None):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_controller_model_grad_dev)."""
+        _lib.check(self._L.lqmpc_controller_model_grad_dev(self._live(), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus), _ptr(dgu0), _ptr(dgVN),
+                                                           _ptr(dgA), _ptr(dgB), _ptr(dgx0)))
 
     def rollout(self, T, x0, A_true, B_true, want_traj=False):
         """T closed-loop steps of every instance from x0 (nx, Bsz) in one launch, from the controller's present state (its models,
@@ -487,10 +534,12 @@ class BatchController:
         before this returns.  Device tensors (.shape, .data_ptr(), contiguous float64; idx an int32 device tensor of length m or
         None): enqueued like a step, returns at once, the caller keeps them alive until the stream has passed and answers for
         "distinct and in range".  Listed instances step with the new model under the current references; the others keep every
-        bit, and all carried active sets are kept (reset() forgets them)."""
+        bit, and all carried active sets are kept (reset() forgets them).  Every call raises model_version by one: a plan taken
+        before it no longer belongs to the controller's models (model_grad reads those)."""
         c = self._live()
         if hasattr(A, "data_ptr") != hasattr(B, "data_ptr"):
             raise ValueError("A and B must both be numpy arrays or both be device tensors")
+        self.model_version += 1
         if not hasattr(A, "data_ptr"):
             A, B, idx, m = _model_update_args(self.nx, self.nu, self.Bsz, A, B, idx)
             _lib.check(self._L.lqmpc_controller_set_model(c, m, _ptr(idx), _ptr(A), _ptr(B)))

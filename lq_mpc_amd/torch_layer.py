@@ -3,14 +3,21 @@
     layer = MPCLayer(N, A, B, Q, R, P, lb, ub)          # A (nx, nx, Bsz), B (nx, nu, Bsz): numpy arrays or fp64 device tensors
     u0, VN = layer(x)                                    # x (nx, Bsz) fp64 device tensor -> u0 (nu, Bsz), VN (Bsz,)
     loss(u0, VN).backward()                              # x.grad through the local feedback law and the value gradient
+    u0, VN = layer(x, A, B)                              # A, B fp64 device tensors, possibly requires_grad: the layer's new model
+    loss(u0, VN).backward()                              # x.grad, and A.grad, B.grad through the model of every instance
 
 Forward is one lqmpc_controller_step_sens_dev on the tensors' own pointers: the QP of every instance, then the post-pass that returns
 K_0 = d u_0 / d x and dV_N / d x on the face the plan ends on.  Backward is  grad_x = K_0' grad_u0 + dV_dx grad_VN, a torch einsum.
+With A and B given, forward first replaces the controller's models in place (set_model, device flavour) and keeps the plan, its
+states and the status; backward adds one lqmpc_controller_model_grad_dev (csrc/lqmpc_grad.hip: the adjoint LQ problem on the plan's
+face), which returns grad_A and grad_B.  That call reads the controller's own copies of the models, so backward raises if any
+set_model, through the layer or on layer.controller, came between the forward and its backward.
 The solver handle is created on torch's current stream (lqmpc_create_on_stream), so everything is ordered with the surrounding torch
 work on that stream and nothing waits for the host, in forward or in backward.  Use the layer under the stream it was made under.
 
 The law of a box-constrained MPC is piecewise affine: the gradient is that of the critical region x lies in, exact inside it and
-one-sided on its border.  Parameters (A, B, weights, box, references) are data, not differentiated.
+one-sided on its border.  The model (A, B) is differentiated per instance; the weights, the box and the references are shared by the
+batch and are data, not differentiated.
 """
 import numpy as np
 import torch
@@ -42,8 +49,52 @@ class _MPCStep(torch.autograd.Function):
         return grad_x, None
 
 
+class _MPCStepModel(torch.autograd.Function):
+    """the step under new models A, B: differentiable in x, A and B"""
+
+    @staticmethod
+    def forward(ctx, x, A, B, ctl):
+        nx, nu, N, Bsz = ctl.nx, ctl.nu, ctl.N, ctl.Bsz
+        if x.dtype != torch.float64 or not x.is_cuda or tuple(x.shape) != (nx, Bsz):
+            raise ValueError(f"x must be a float64 device tensor of shape ({nx}, {Bsz})")
+        for M, shape in ((A, (nx, nx, Bsz)), (B, (nx, nu, Bsz))):
+            if M.dtype != torch.float64 or not M.is_cuda or tuple(M.shape) != shape:
+                raise ValueError(f"A and B must be float64 device tensors of shapes ({nx}, {nx}, {Bsz}) and ({nx}, {nu}, {Bsz})")
+        x = x.detach().contiguous()
+        ctl.set_model(A.detach().contiguous(), B.detach().contiguous())
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=x.device)
+        u0, VN, K0, dV = new(nu, Bsz), new(Bsz), new(nu, nx, Bsz), new(nx, Bsz)
+        Up, Xp, st = new(nu, N, Bsz), new(nx, N + 1, Bsz), torch.empty(Bsz, dtype=torch.int32, device=x.device)
+        ctl.step_sens_dev(x, u0, K0, dV, dUplan=Up, dXplan=Xp, dVN=VN, dstatus=st)
+        ctx.save_for_backward(K0, dV, Up, Xp, st)
+        ctx.ctl, ctx.model_version = ctl, ctl.model_version
+        return u0, VN
+
+    @staticmethod
+    def backward(ctx, grad_u0, grad_VN):
+        K0, dV, Up, Xp, st = ctx.saved_tensors
+        ctl = ctx.ctl
+        if ctl.model_version != ctx.model_version:
+            raise RuntimeError("MPCLayer: the controller's models were replaced (set_model) between this forward and its backward; "
+                               "the gradient with respect to A and B would be that of another model")
+        grad_x = None
+        if grad_u0 is not None:
+            grad_x = torch.einsum("kab,kb->ab", K0, grad_u0)
+        if grad_VN is not None:
+            g = dV * grad_VN.unsqueeze(0)
+            grad_x = g if grad_x is None else grad_x + g
+        grad_A = grad_B = None
+        if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and (grad_u0 is not None or grad_VN is not None):
+            grad_A = torch.empty((ctl.nx, ctl.nx, ctl.Bsz), dtype=torch.float64, device=Xp.device)
+            grad_B = torch.empty((ctl.nx, ctl.nu, ctl.Bsz), dtype=torch.float64, device=Xp.device)
+            ctl.model_grad_dev(Up, Xp, grad_A, grad_B, dstatus=st,
+                               dgu0=None if grad_u0 is None else grad_u0.contiguous(), dgVN=None if grad_VN is None else grad_VN.contiguous())
+        return grad_x, grad_A, grad_B, None
+
+
 class MPCLayer(torch.nn.Module):
-    """u0, VN = MPCLayer(N, A, B, Q, R, P, lb, ub)(x) around a BatchController; options are the solver's (BatchSolver.set_options)."""
+    """u0, VN = MPCLayer(N, A, B, Q, R, P, lb, ub)(x) around a BatchController; options are the solver's (BatchSolver.set_options).
+    layer(x, A, B) steps under the models A, B (they become the controller's) and is differentiable in them as well."""
 
     def __init__(self, N, A, B, Q, R, P, lb, ub, x_ref=None, u_ref=None, **options):
         super().__init__()
@@ -53,8 +104,12 @@ class MPCLayer(torch.nn.Module):
             A, B = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(B, dtype=np.float64)
         self.controller = BatchController(self.solver, N, A, B, Q, R, P, lb, ub, x_ref, u_ref)
 
-    def forward(self, x):
-        return _MPCStep.apply(x, self.controller)
+    def forward(self, x, A=None, B=None):
+        if A is None and B is None:
+            return _MPCStep.apply(x, self.controller)
+        if A is None or B is None:
+            raise ValueError("give both A and B, or neither")
+        return _MPCStepModel.apply(x, A, B, self.controller)
 
     def close(self):
         self.controller.close()
