@@ -75,7 +75,14 @@ __device__ __forceinline__ double inv2(double M, int r, int c, int o)
 }
 
 // Inverse of the leading NUP x NUP block of the register matrix Re (symmetric positive definite), zero elsewhere.
-template <int NUP>
+// REFINE (the QP set-up; 3 and 4 inputs only): the block form multiplies explicit inverses, E^-1 F S^-1 and S^-1 F'E^-1 F S^-1, so its
+// residual is eps cond(Re)^2 where the adjugate of a 2 x 2 block leaves eps cond(Re) -- and K = X B'Sg A, W = 1/2 T D^-1 T' and G inherit it
+// (cheap control with nearly collinear inputs, cond(Re) 1e5 .. 1e6: u off by 1e-7 .. 1e-5 h, tests/test_gpu_qp_hard.py).  Two Newton steps
+// X <- X (2I - Re X) square the residual twice (three products each: the transpose of X is one of them, X (2I - Re X) with the X' a
+// product reads would leave the asymmetry of X in the residual), then the LEFT residual I - X Re is measured, the one K = X F inherits:
+// |I - X Re|_F >= 2^-32 (cond(Re) beyond about 1e6, or a block form too far off for Newton to contract) makes the inverse NaN, and the
+// instance is handed back like one whose Re is not positive definite.
+template <int NUP, bool REFINE = false>
 __device__ __forceinline__ double small_inverse(double Re, int r, int c)
 {
     if constexpr (NUP == 1) {
@@ -93,7 +100,18 @@ __device__ __forceinline__ double small_inverse(double Re, int r, int c)
         const double FtEi = mm4(Fb, Ei);                               // F'E^-1      (rows 2-3, columns 0-1)
         const double X = mm4(FtEi, Si);                                // E^-1 F S^-1
         const double Xt = mm4(Si, FtEi);                               // S^-1 F'E^-1
-        return mm4(Xt, FtEi, Ei) - X - Xt + Si;
+        const double X0 = mm4(Xt, FtEi, Ei) - X - Xt + Si;
+        if constexpr (!REFINE) return X0;
+        const double I4 = (r == c) ? 1.0 : 0.0;
+        double Xr = X0;
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const double E = I4 - mm4(Re, Xr);                         // I - Re'X: the product reads Re', and Re = R + B'(Sg B) is symmetric only up to rounding (eps |Re|), an eps cond(Re) in E like the rounding of the product itself; all 4 x 4: Re is padded SPD
+            Xr = mm4(mm4(Xr, I4), I4 + E);                             // (X')' (2I - Re X)
+        }
+        const double EL = I4 - mm4(mm4(Xr, I4), Re);                   // I - X Re
+        const double f2 = mm4(mm4(EL * EL, 1.0), 1.0);                 // its Frobenius norm squared, in every lane
+        return (f2 < 0x1p-64) ? Xr : __builtin_nan("");
     }
 }
 
@@ -418,7 +436,7 @@ __device__ __forceinline__ void r16_setup_mfma(const SetupArgs &p, long long bg,
             for (int k = 0; k < TX; ++k) v = mm4(Bp[k], SA[k][b], v);
             F[b] = v;
         }
-        const double R0 = small_inverse<NUP>(Re, r, c);
+        const double R0 = small_inverse<NUP, true>(Re, r, c);
 #pragma unroll
         for (int b = 0; b < TX; ++b) K[b] = mm4(R0, F[b]);
         if constexpr (ROLL && off != 0) {                             // (off == 0: K' is Ktp below, as it stands)
