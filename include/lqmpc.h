@@ -300,6 +300,50 @@ int lqmpc_model_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t B
                                const double *dgu0, const double *dgVN,
                                double *dgA, double *dgB, double *dgx0);
 
+/* ---- the gradient of a loss on (u_0, V_N) with respect to the data the batch shares: weights, references, box ----
+ * Inputs as lqmpc_model_grad_batch: what a plan or sens call wrote (Uplan, Xplan, status; status may be NULL = all 0) and the
+ * cotangents gu0 (nu, Bsz) and gVN (Bsz) (either may be NULL = zero, not both).  With e_i = x_i - x_ref[:, i-1], d_i = u_i - u_ref[:, i],
+ * the adjoint plan (ut, xt) and the costates l, lt of the model gradient, r_i = 2 R d_i + B'l_{i+1}, rt_i = 2 R ut_i + B'lt_{i+1}:
+ *     gQ    = gVN x0 x0' + sum_{i=1}^{N-1} (gVN e_i e_i' - xt_i e_i' - e_i xt_i')     gP = the same term at i = N
+ *     gR    = sum_{i=0}^{N-1} (gVN d_i d_i' - ut_i d_i' - d_i ut_i')
+ *     gxref[:, i-1] = 2 Q (xt_i - gVN e_i)  (P at i = N)                               guref[:, i] = 2 R (ut_i - gVN d_i)
+ *     gub[k] = sum over the entries (i, k) of the plan on the upper bound of gVN r_i[k] - rt_i[k] + (i == 0 ? gu0[k] : 0); glb likewise
+ * gQ, gR, gP are the derivatives with the entries of the matrix taken as independent; they are symmetric, and a symmetric change dQ
+ * changes the loss by <gQ, dQ>.  The face is the one the plan reports, by the rule of lqmpc_solve_sens_batch (an entry equal, bit
+ * for bit, to lb_k or c_k - h_k is on the lower bound, to ub_k or c_k + h_k on the upper); the gVN parts hold on every face.
+ * reduce == 0: every output per instance, instance-minor -- gQ[(a*nx + c)*Bsz + b], gR[(k*nu + l)*Bsz + b], gP like gQ, glb[k*Bsz + b],
+ *   gub likewise, gxref[(a*N + i)*Bsz + b], guref[(k*N + i)*Bsz + b]; an instance with status 2 gets NaN in all of them; nskipped
+ *   is not written.
+ * reduce != 0: every output in the shape of its parameter, row-major (gQ nx x nx, ..., gxref nx x N), the SUM over the batch, formed
+ *   on chip in a fixed order without atomics: the same data give the same bits.  An instance with status 2 adds nothing and is
+ *   counted in *nskipped (may be NULL).
+ * Any output may be NULL, not all (all NULL, or both cotangents NULL: LQMPC_ERR_BAD_ARG before anything is enqueued).  The call is the
+ * post-pass alone -- one launch of lqmpc_cost_grad_kernel on the handle's stream (with reduce a second, small one), no solve -- so A,
+ * B, the weights, the box and the references must be those of the call that wrote the plan; lqmpc_last_kernel is left naming the
+ * solve kernel.  An instance whose stage-0 inputs all sit on bounds and whose gVN is 0 gets exact 0.0 in gQ, gR, gP, gxref, guref and
+ * gu0[k] in glb[k] + gub[k].  A shape whose LDS image would not fit 160 KiB is refused with LQMPC_ERR_UNSUPPORTED: none within the
+ * build limits with reduce == 0; with reduce != 0 the 48 shapes DESIGN.md section 4.12 lists (nx >= 14 with long horizons).
+ * lqmpc_cost_grad_blocks: the number of wavefronts the kernel is launched with, a function of the shape and Bsz only (0: bad dims). */
+int lqmpc_cost_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                          const double *A, const double *B,
+                          const double *Q, const double *R, const double *P,
+                          const double *lb, const double *ub,
+                          const double *x_ref, const double *u_ref,
+                          const double *Uplan, const double *Xplan, const int32_t *status,
+                          const double *gu0, const double *gVN, int reduce,
+                          double *gQ, double *gR, double *gP, double *glb, double *gub, double *gxref, double *guref,
+                          int64_t *nskipped);
+int lqmpc_cost_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                              const double *dA, const double *dB,
+                              const double *Q, const double *R, const double *P,
+                              const double *lb, const double *ub,
+                              const double *x_ref, const double *u_ref,
+                              const double *dUplan, const double *dXplan, const int32_t *dstatus,
+                              const double *dgu0, const double *dgVN, int reduce,
+                              double *dgQ, double *dgR, double *dgP, double *dglb, double *dgub, double *dgxref, double *dguref,
+                              int64_t *dnskipped);
+int64_t lqmpc_cost_grad_blocks(int nx, int nu, int N, int64_t Bsz, int reduce);
+
 /* ---- LQ_MPC_Simulator.simulate, batched (utils_class.py:245-285) ----
  * The model (A,B) drives the QP, the plant (A_true,B_true) drives the state.
  * true_per_instance == 0: A_true/B_true are single HOST matrices shared by the batch
@@ -434,6 +478,8 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
  * model_grad: lqmpc_model_grad_batch on the controller's own copies of A and B (on workgroup records the heads of the records) and its
  *   current references, for a plan one of its steps wrote since the last set_model / set_reference.  Read-only on the controller:
  *   the next step is bit for bit what it is without the call.
+ * cost_grad: lqmpc_cost_grad_batch likewise, on the controller's models, weights, box and current references (those of the last
+ *   set_reference).  Read-only on the controller as well.
  * reset: forget the stored active sets (the next step starts cold).  bytes: HBM held by the controller.  kernel: the kernel its
  *   steps launch (contains "ctl"), or for a pass-through controller the kernel its last step ran.  destroy: NULL is fine.
  * set_reference: new references for every later step, x_ref (nx x N) and u_ref (nu x N) HOST, row-major, NULL = zeros -- for a loop
@@ -499,6 +545,14 @@ int lqmpc_controller_model_grad(lqmpc_controller *c, const double *Uplan, const 
                                 const double *gu0, const double *gVN, double *gA, double *gB, double *gx0);
 int lqmpc_controller_model_grad_dev(lqmpc_controller *c, const double *dUplan, const double *dXplan, const int32_t *dstatus,
                                     const double *dgu0, const double *dgVN, double *dgA, double *dgB, double *dgx0);
+int lqmpc_controller_cost_grad(lqmpc_controller *c, const double *Uplan, const double *Xplan, const int32_t *status,
+                               const double *gu0, const double *gVN, int reduce,
+                               double *gQ, double *gR, double *gP, double *glb, double *gub, double *gxref, double *guref,
+                               int64_t *nskipped);
+int lqmpc_controller_cost_grad_dev(lqmpc_controller *c, const double *dUplan, const double *dXplan, const int32_t *dstatus,
+                                   const double *dgu0, const double *dgVN, int reduce,
+                                   double *dgQ, double *dgR, double *dgP, double *dglb, double *dgub, double *dgxref, double *dguref,
+                                   int64_t *dnskipped);
 int lqmpc_controller_rollout(lqmpc_controller *c, int T, const double *x0,
                              const double *A_true, const double *B_true, int true_per_instance,
                              double *JT, double *X, double *U, int32_t *status, int32_t *iters);

@@ -38,6 +38,8 @@ EXPORTS = [
     "lqmpc_jit_compile_plan",
     "lqmpc_solve_sens_batch", "lqmpc_solve_sens_batch_dev", "lqmpc_controller_step_sens", "lqmpc_controller_step_sens_dev",
     "lqmpc_model_grad_batch", "lqmpc_model_grad_batch_dev", "lqmpc_controller_model_grad", "lqmpc_controller_model_grad_dev",
+    "lqmpc_cost_grad_batch", "lqmpc_cost_grad_batch_dev", "lqmpc_controller_cost_grad", "lqmpc_controller_cost_grad_dev",
+    "lqmpc_cost_grad_blocks",
 ]
 
 
@@ -101,6 +103,10 @@ def lib():
     L.lqmpc_solve_sens_batch_dev.argtypes = solve_args + [P] * 5
     L.lqmpc_model_grad_batch.argtypes = dims + [P] * 17
     L.lqmpc_model_grad_batch_dev.argtypes = dims + [P] * 17
+    L.lqmpc_cost_grad_batch.argtypes = dims + [P] * 14 + [ctypes.c_int] + [P] * 8
+    L.lqmpc_cost_grad_batch_dev.argtypes = dims + [P] * 14 + [ctypes.c_int] + [P] * 8
+    L.lqmpc_cost_grad_blocks.argtypes = [ctypes.c_int] * 3 + [ctypes.c_int64, ctypes.c_int]
+    L.lqmpc_cost_grad_blocks.restype = ctypes.c_int64
     roll_args = dims + [ctypes.c_int] + [P] * 10 + [ctypes.c_int] + [P] * 7
     L.lqmpc_rollout_batch.argtypes = roll_args
     L.lqmpc_rollout_batch_dev.argtypes = roll_args
@@ -131,6 +137,8 @@ def lib():
     L.lqmpc_controller_step_sens_dev.argtypes = [_H] + [P] * 10
     L.lqmpc_controller_model_grad.argtypes = [_H] + [P] * 8
     L.lqmpc_controller_model_grad_dev.argtypes = [_H] + [P] * 8
+    L.lqmpc_controller_cost_grad.argtypes = [_H] + [P] * 5 + [ctypes.c_int] + [P] * 8
+    L.lqmpc_controller_cost_grad_dev.argtypes = [_H] + [P] * 5 + [ctypes.c_int] + [P] * 8
     ctl_roll_args = [_H, ctypes.c_int, P, P, P, ctypes.c_int] + [P] * 5
     L.lqmpc_controller_rollout.argtypes = ctl_roll_args
     L.lqmpc_controller_rollout_dev.argtypes = ctl_roll_args

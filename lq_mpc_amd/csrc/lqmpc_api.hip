@@ -54,6 +54,7 @@ struct lqmpc_handle {
     int hist_turn = 0;               // which set the next probe counts into
     DevBuf st2, it2;                 // lqmpc_sweep_batch_dev without a fused kernel: status / iters of the max-V_N pass
     DevBuf sens_u, sens_x, sens_st;  // lqmpc_*_sens*: the plan, its states and the status where the caller passed NULL
+    DevBuf cgrad_part;               // lqmpc_*_cost_grad* with reduce: the partial sums of every wavefront
     DevBuf arena;                    // host-flavour staging (Stager): every array of the call in one block
     HostBuf arena_pin;               // ... its pinned image, for the small calls that go up and come back in one copy each
     HostBuf shared_pin[2];           // source of the shared block's upload
@@ -185,7 +186,7 @@ int lqmpc_destroy(lqmpc_handle *h)
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (DevBuf *b : {&h->shared, &h->ws, &h->key, &h->perm, &h->rec, &h->fail, &h->st2, &h->it2, &h->sens_u, &h->sens_x, &h->sens_st, &h->arena}) if (b->p) (void)hipFree(b->p);
+    for (DevBuf *b : {&h->shared, &h->ws, &h->key, &h->perm, &h->rec, &h->fail, &h->st2, &h->it2, &h->sens_u, &h->sens_x, &h->sens_st, &h->cgrad_part, &h->arena}) if (b->p) (void)hipFree(b->p);
     for (HostBuf *b : {&h->arena_pin, &h->shared_pin[0], &h->shared_pin[1]}) {
         if (b->p) (void)hipHostFree(b->p);
         if (b->ev) (void)hipEventDestroy(b->ev);
@@ -731,6 +732,63 @@ static int grad_launch(lqmpc_handle *h, const Call &c, lqmpc::GradParams &g)
     return 0;
 }
 
+// The cost-gradient calls (lqmpc_cost_grad_batch_dev, lqmpc_controller_cost_grad_dev): the checks, the shared block of `c` (the one the
+// plan call before it uploaded, so nothing is copied again) and one launch of lqmpc_cost_grad_kernel -- with `reduce` on a bounded grid
+// that leaves its partial sums in the handle's own block, followed by the kernel that adds them.  No solve, no plan: nothing is routed
+// or compiled, and lqmpc_last_kernel is left naming the solve kernel.
+static int cgrad_nulls(const void *owner, const double *Uplan, const double *Xplan, const double *gu0, const double *gVN, double *const out[7])
+{
+    if (!owner || !Uplan || !Xplan) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    bool any = false;
+    for (int k = 0; k < 7; ++k) any = any || out[k];
+    if (!any) return fail(LQMPC_ERR_BAD_ARG, "every output is NULL");
+    if (!gu0 && !gVN) return fail(LQMPC_ERR_BAD_ARG, "gu0 and gVN are both NULL: there is no cotangent");
+    return 0;
+}
+
+static int cgrad_check(const void *owner, const Call *c, int nx, int nu, int N, const double *Uplan, const double *Xplan, const double *gu0,
+                       const double *gVN, int reduce, double *const out[7])
+{
+    int rc0 = cgrad_nulls(owner, Uplan, Xplan, gu0, gVN, out);
+    if (rc0) return rc0;
+    if (c) {                                                    // (a controller's own data passed these checks when it was made)
+        const int rc = check_call(*c);
+        if (rc) return rc;
+    }
+    if (!lqmpc::cgrad_fits(nx, nu, N, reduce ? 1 : 0)) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "lqmpc_cost_grad_kernel needs %zu bytes of LDS at (%d,%d,%d)%s: over 160 KiB",
+                 lqmpc::cgrad_lds_bytes(nx, nu, N, reduce ? 1 : 0), nx, nu, N, reduce ? " with reduce" : "");
+        return fail(LQMPC_ERR_UNSUPPORTED, buf);
+    }
+    return 0;
+}
+
+static int cgrad_launch(lqmpc_handle *h, const Call &c, lqmpc::CGradParams &g)
+{
+    int rc = cgrad_check(h, &c, c.nx, c.nu, c.N, g.Uplan, g.Xplan, g.gu0, g.gVN, g.reduce, g.out);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    rc = upload_shared(h, c, nullptr, g.so);
+    if (rc) return rc;
+    g.sh = (const double *)h->shared.p;
+    if (g.reduce) {
+        rc = ensure(h, h->cgrad_part, lqmpc::cgrad_part_bytes(c.nx, c.nu, c.N, c.Bsz));
+        if (rc) return rc;
+        g.part = (double *)h->cgrad_part.p;
+    }
+    if (!lqmpc::launch_cgrad(g, h->stream)) return fail(LQMPC_ERR_HIP, "lqmpc_cost_grad_kernel launch failed");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the element counts of the seven outputs: per instance times Bsz, with reduce as they are
+static void cgrad_counts(int nx, int nu, int N, size_t n[7])
+{
+    n[0] = (size_t)nx * nx; n[1] = (size_t)nu * nu; n[2] = (size_t)nx * nx; n[3] = n[4] = (size_t)nu;
+    n[5] = (size_t)nx * N; n[6] = (size_t)nu * N;
+}
+
 extern "C" {
 
 int lqmpc_reserve(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T)
@@ -800,6 +858,25 @@ int lqmpc_model_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t B
     const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
     lqmpc::GradParams g{nx, nu, N, Bsz, dA, dB, Bsz, 1, dUplan, dXplan, dstatus, nullptr, {}, dgu0, dgVN, dgA, dgB, dgx0};
     return grad_launch(h, c, g);
+}
+
+int lqmpc_cost_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *dA, const double *dB,
+                              const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                              const double *x_ref, const double *u_ref, const double *dUplan, const double *dXplan,
+                              const int32_t *dstatus, const double *dgu0, const double *dgVN, int reduce, double *dgQ, double *dgR,
+                              double *dgP, double *dglb, double *dgub, double *dgxref, double *dguref, int64_t *dnskipped)
+{
+    if (!h || !dA || !dB) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
+    lqmpc::CGradParams g{nx, nu, N, Bsz, dA, dB, Bsz, 1, dUplan, dXplan, dstatus, nullptr, {}, dgu0, dgVN, reduce ? 1 : 0,
+                         {dgQ, dgR, dgP, dglb, dgub, dgxref, dguref}, (long long *)dnskipped, nullptr};
+    return cgrad_launch(h, c, g);
+}
+
+int64_t lqmpc_cost_grad_blocks(int nx, int nu, int N, int64_t Bsz, int reduce)
+{
+    if (check_dims(nx, nu, N, Bsz)) return 0;
+    return lqmpc::cgrad_blocks(nx, nu, N, Bsz, reduce ? 1 : 0);
 }
 
 int lqmpc_rollout_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *dA, const double *dB,
@@ -1029,6 +1106,36 @@ int lqmpc_model_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, 
     s.out(gA, b * nx * nx, dgA); s.out(gB, b * nx * nu, dgB); s.out(gx0, b * nx, dgx);
     rc = s.upload();
     if (!rc) rc = lqmpc_model_grad_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, x_ref, u_ref, dUp, dXp, dst, dgu, dgV, dgA, dgB, dgx);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_cost_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B,
+                          const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                          const double *x_ref, const double *u_ref, const double *Uplan, const double *Xplan, const int32_t *status,
+                          const double *gu0, const double *gVN, int reduce, double *gQ, double *gR, double *gP, double *glb, double *gub,
+                          double *gxref, double *guref, int64_t *nskipped)
+{
+    if (!A || !B) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
+    double *const outs[7] = {gQ, gR, gP, glb, gub, gxref, guref};
+    int rc = cgrad_check(h, &c, nx, nu, N, Uplan, Xplan, gu0, gVN, reduce, outs);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)Bsz, per = reduce ? 1 : b;
+    size_t n[7];
+    cgrad_counts(nx, nu, N, n);
+    const double *dA, *dB, *dUp, *dXp, *dgu, *dgV;
+    const int32_t *dst;
+    double *d[7];
+    int64_t *dns;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(Uplan, b * nu * N, dUp); s.in(Xplan, b * nx * (N + 1), dXp);
+    s.in(status, b, dst); s.in(gu0, b * nu, dgu); s.in(gVN, b, dgV);
+    for (int k = 0; k < 7; ++k) s.out(outs[k], n[k] * per, d[k]);
+    s.out(reduce ? nskipped : (int64_t *)nullptr, 1, dns);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_cost_grad_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, x_ref, u_ref, dUp, dXp, dst, dgu, dgV, reduce,
+                                            d[0], d[1], d[2], d[3], d[4], d[5], d[6], dns);
     return rc ? rc : s.finish();
 }
 
@@ -1553,6 +1660,51 @@ int lqmpc_controller_model_grad(lqmpc_controller *c, const double *Uplan, const 
     s.out(gA, b * nx * nx, dgA); s.out(gB, b * nx * nu, dgB); s.out(gx0, b * nx, dgx);
     rc = s.upload();
     if (!rc) rc = lqmpc_controller_model_grad_dev(c, dUp, dXp, dst, dgu, dgV, dgA, dgB, dgx);
+    return rc ? rc : s.finish();
+}
+
+// read-only on the controller: its copies of A and B (on workgroup records the heads of the records) and its current references
+int lqmpc_controller_cost_grad_dev(lqmpc_controller *c, const double *dUplan, const double *dXplan, const int32_t *dstatus,
+                                   const double *dgu0, const double *dgVN, int reduce, double *dgQ, double *dgR, double *dgP, double *dglb,
+                                   double *dgub, double *dgxref, double *dguref, int64_t *dnskipped)
+{
+    double *const outs[7] = {dgQ, dgR, dgP, dglb, dgub, dgxref, dguref};
+    const int rc = cgrad_nulls(c, dUplan, dXplan, dgu0, dgVN, outs);
+    if (rc) return rc;
+    lqmpc::CGradParams g{c->nx, c->nu, c->N, c->Bsz, (const double *)c->A, (const double *)c->B, c->Bsz, 1, dUplan, dXplan, dstatus,
+                         nullptr, {}, dgu0, dgVN, reduce ? 1 : 0, {dgQ, dgR, dgP, dglb, dgub, dgxref, dguref}, (long long *)dnskipped, nullptr};
+    if (!c->A) {
+        const lqmpc::WgCtlRec L = lqmpc::wg_ctl_rec_layout(c->nx, c->nu, c->N);
+        g.A = (const double *)c->rec + L.oA; g.B = (const double *)c->rec + L.oB;
+        g.sE = 1; g.sI = L.stride;
+    }
+    return cgrad_launch(c->h, ctl_call(c), g);
+}
+
+int lqmpc_controller_cost_grad(lqmpc_controller *c, const double *Uplan, const double *Xplan, const int32_t *status,
+                               const double *gu0, const double *gVN, int reduce, double *gQ, double *gR, double *gP, double *glb,
+                               double *gub, double *gxref, double *guref, int64_t *nskipped)
+{
+    double *const outs[7] = {gQ, gR, gP, glb, gub, gxref, guref};
+    int rc = cgrad_nulls(c, Uplan, Xplan, gu0, gVN, outs);
+    if (rc) return rc;
+    rc = cgrad_check(c, nullptr, c->nx, c->nu, c->N, Uplan, Xplan, gu0, gVN, reduce, outs);
+    if (rc) return rc;
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)c->Bsz, nx = (size_t)c->nx, nu = (size_t)c->nu, N = (size_t)c->N, per = reduce ? 1 : b;
+    size_t n[7];
+    cgrad_counts(c->nx, c->nu, c->N, n);
+    const double *dUp, *dXp, *dgu, *dgV;
+    const int32_t *dst;
+    double *d[7];
+    int64_t *dns;
+    s.in(Uplan, b * nu * N, dUp); s.in(Xplan, b * nx * (N + 1), dXp); s.in(status, b, dst); s.in(gu0, b * nu, dgu); s.in(gVN, b, dgV);
+    for (int k = 0; k < 7; ++k) s.out(outs[k], n[k] * per, d[k]);
+    s.out(reduce ? nskipped : (int64_t *)nullptr, 1, dns);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_controller_cost_grad_dev(c, dUp, dXp, dst, dgu, dgV, reduce, d[0], d[1], d[2], d[3], d[4], d[5], d[6], dns);
     return rc ? rc : s.finish();
 }
 

@@ -93,4 +93,29 @@ size_t grad_lds_bytes(int nx, int nu, int N);
 bool grad_fits(int nx, int nu, int N);
 bool launch_grad(const GradParams &p, hipStream_t stream);
 
+// lqmpc_cgrad.hip: the post-pass of lqmpc_cost_grad_batch / lqmpc_controller_cost_grad -- from the same inputs, the gradient with
+// respect to the data the batch shares: the weights Q, R, P, the box lb, ub and the references x_ref, u_ref.  Per instance
+// (reduce = 0: every output instance-minor) or summed over the batch on chip (reduce = 1: every output in the shape of its parameter,
+// row-major; cgrad_blocks wavefronts each leave one vector of partial sums in `part`, a second kernel adds them in a fixed order).
+struct CGradParams {
+    int nx, nu, N;
+    long long Bsz;
+    const double *A, *B;                  // as SensParams: element e of instance b at A[e * sE + b * sI]
+    long long sE, sI;
+    const double *Uplan, *Xplan;          // what a plan or sens call wrote, instance-minor
+    const int *status;                    // its status (2: NaN in every output of the instance / left out of the sums); null: all 0
+    const double *sh;                     // shared block (device): Q, R, P, the box, x_ref and u_ref at the offsets so
+    SharedOff so;
+    const double *gu0, *gVN;              // d loss / d u_0 (nu, Bsz) and d loss / d V_N (Bsz); either may be null = zero
+    int reduce;
+    double *out[7];                       // gQ, gR, gP, glb, gub, gxref, guref; any may be null, not all
+    long long *nskipped;                  // reduce: the number of instances with status 2 (device); may be null
+    double *part;                         // reduce: cgrad_part_bytes of the handle's own block, entry e of wavefront g at part[e * blocks + g]
+};
+size_t cgrad_lds_bytes(int nx, int nu, int N, int reduce);
+bool cgrad_fits(int nx, int nu, int N, int reduce);
+long long cgrad_blocks(int nx, int nu, int N, long long Bsz, int reduce);   // the grid: a function of the shape and Bsz only
+size_t cgrad_part_bytes(int nx, int nu, int N, long long Bsz);
+bool launch_cgrad(const CGradParams &p, hipStream_t stream);
+
 }  // namespace lqmpc

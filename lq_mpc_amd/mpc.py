@@ -101,6 +101,24 @@ def _model_update_args(nx, nu, Bsz, A, B, idx):
     return A, B, np.ascontiguousarray(idx, dtype=np.int32), m
 
 
+
+_CGRAD_KEYS = ("g_Q", "g_R", "g_P", "g_lb", "g_ub", "g_xref", "g_uref")
+
+
+def _cgrad_outputs(nx, nu, N, Bsz, reduce):
+    """the seven host outputs of a cost-gradient call, per instance (instance axis last) or reduced (the parameter's own shape)"""
+    shapes = ((nx, nx), (nu, nu), (nx, nx), (nu,), (nu,), (nx, N), (nu, N))
+    return {k: np.empty(sh if reduce else sh + (Bsz,)) for k, sh in zip(_CGRAD_KEYS, shapes)}
+
+
+def _cgrad_dev_ptrs(outs):
+    """the seven device outputs of a cost-gradient call from a dict keyed like the host flavour's result; missing or None: NULL"""
+    unknown = set(outs) - set(_CGRAD_KEYS)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}: the keys are {_CGRAD_KEYS}")
+    return [_ptr(outs.get(k)) for k in _CGRAD_KEYS]
+
+
 class BatchSolver:
     """One handle = one GPU + one stream (include/lqmpc.h).  Not thread-safe."""
 
@@ -340,6 +358,45 @@ class BatchSolver:
                                                       _ptr(ub), _ptr(x_ref), _ptr(u_ref), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus),
                                                       _ptr(dgu0), _ptr(dgVN), _ptr(dgA), _ptr(dgB), _ptr(dgx0)))
 
+    def cost_grad_batch(self, N, A, B, Q, R, P, lb, ub, U_plan, X_plan, status=None, g_u0=None, g_VN=None, x_ref=None, u_ref=None,
+                        reduce=False):
+        """The gradient of a loss on (u_0, V_N) with respect to the data the batch shares -- the weights, the references and the box
+        -- on the face the plan reports (lqmpc_cost_grad_batch); arguments as model_grad_batch.  Returns {"g_Q", "g_R", "g_P", "g_lb",
+        "g_ub", "g_xref", "g_uref"}: per instance with the instance axis last ((nx, nx, Bsz), ..., (nx, N, Bsz)), or with reduce=True
+        the sum over the batch in the shape of the parameter, formed on the GPU in a fixed order, and "skipped", the number of
+        instances with status 2, which add nothing.  g_Q, g_R, g_P take the entries of the matrix as independent (they are
+        symmetric).  The post-pass alone: no solve."""
+        A, B, nx, nu, Bsz = self._dims(A, B)
+        Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
+        lb, ub = _f64(lb, (nu,)), _f64(ub, (nu,))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        U_plan, X_plan = _f64(U_plan, (nu, N, Bsz)), _f64(X_plan, (nx, N + 1, Bsz))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(Bsz)
+        g_u0 = None if g_u0 is None else _f64(g_u0, (nu, Bsz))
+        g_VN = None if g_VN is None else _f64(g_VN, (Bsz,))
+        out = _cgrad_outputs(nx, nu, N, Bsz, reduce)
+        skipped = np.zeros(1, dtype=np.int64)
+        _lib.check(self._L.lqmpc_cost_grad_batch(self._h, nx, nu, N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P), _ptr(lb), _ptr(ub),
+                                                 _ptr(x_ref), _ptr(u_ref), _ptr(U_plan), _ptr(X_plan), _ptr(status), _ptr(g_u0),
+                                                 _ptr(g_VN), int(bool(reduce)), *[_ptr(out[k]) for k in _CGRAD_KEYS], _ptr(skipped)))
+        if reduce:
+            out["skipped"] = int(skipped[0])
+        return out
+
+    def cost_grad_batch_dev(self, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dUplan, dXplan, outs, dstatus=None, dgu0=None, dgVN=None,
+                            x_ref=None, u_ref=None, reduce=False, dskipped=None):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_cost_grad_batch_dev).  outs: a dict
+        with any of the keys g_Q, g_R, g_P, g_lb, g_ub, g_xref, g_uref (at least one); dskipped: an int64 device scalar."""
+        Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        _lib.check(self._L.lqmpc_cost_grad_batch_dev(self._h, nx, nu, N, Bsz, _ptr(dA), _ptr(dB), _ptr(Q), _ptr(R), _ptr(P), _ptr(lb),
+                                                     _ptr(ub), _ptr(x_ref), _ptr(u_ref), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus),
+                                                     _ptr(dgu0), _ptr(dgVN), int(bool(reduce)), *_cgrad_dev_ptrs(outs), _ptr(dskipped)))
+
+    def cost_grad_blocks(self, nx, nu, N, Bsz, reduce=True):
+        """the number of wavefronts a cost-gradient call is launched with: a function of the shape and Bsz only"""
+        return int(self._L.lqmpc_cost_grad_blocks(nx, nu, N, Bsz, int(bool(reduce))))
+
     def rollout_batch_dev(self, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dx0, A_true, B_true, dJT,
                           dX=None, dU=None, dstatus=None, diters=None, true_per_instance=False, x_ref=None, u_ref=None):
         Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
@@ -423,6 +480,7 @@ class BatchController:
                         _ptr(x_ref), _ptr(u_ref), ctypes.byref(c)))
         self._c = c
         self.model_version = 0                  # counts set_model calls: what a gradient taken later checks its plan against
+        self.reference_version = 0              # ... and set_reference calls
 
     def _live(self):
         if self._c is None or not self._c.value:
@@ -486,6 +544,28 @@ class BatchController:
         _lib.check(self._L.lqmpc_controller_model_grad_dev(self._live(), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus), _ptr(dgu0), _ptr(dgVN),
                                                            _ptr(dgA), _ptr(dgB), _ptr(dgx0)))
 
+    def cost_grad(self, U_plan, X_plan, status=None, g_u0=None, g_VN=None, reduce=False):
+        """BatchSolver.cost_grad_batch on the controller's own models, weights, box and current references, for a plan one of its
+        steps returned (lqmpc_controller_cost_grad).  Read-only on the controller."""
+        nx, nu, N, Bsz = self.nx, self.nu, self.N, self.Bsz
+        U_plan, X_plan = _f64(U_plan, (nu, N, Bsz)), _f64(X_plan, (nx, N + 1, Bsz))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(Bsz)
+        g_u0 = None if g_u0 is None else _f64(g_u0, (nu, Bsz))
+        g_VN = None if g_VN is None else _f64(g_VN, (Bsz,))
+        out = _cgrad_outputs(nx, nu, N, Bsz, reduce)
+        skipped = np.zeros(1, dtype=np.int64)
+        _lib.check(self._L.lqmpc_controller_cost_grad(self._live(), _ptr(U_plan), _ptr(X_plan), _ptr(status), _ptr(g_u0), _ptr(g_VN),
+                                                      int(bool(reduce)), *[_ptr(out[k]) for k in _CGRAD_KEYS], _ptr(skipped)))
+        if reduce:
+            out["skipped"] = int(skipped[0])
+        return out
+
+    def cost_grad_dev(self, dUplan, dXplan, outs, dstatus=None, dgu0=None, dgVN=None, reduce=False, dskipped=None):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_controller_cost_grad_dev); outs and
+        dskipped as BatchSolver.cost_grad_batch_dev."""
+        _lib.check(self._L.lqmpc_controller_cost_grad_dev(self._live(), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus), _ptr(dgu0), _ptr(dgVN),
+                                                          int(bool(reduce)), *_cgrad_dev_ptrs(outs), _ptr(dskipped)))
+
     def rollout(self, T, x0, A_true, B_true, want_traj=False):
         """T closed-loop steps of every instance from x0 (nx, Bsz) in one launch, from the controller's present state (its models,
         weights, box and current references): the dict of BatchSolver.rollout_batch.  A_true (nx, nx) / B_true (nx, nu): one plant
@@ -523,8 +603,11 @@ class BatchController:
     def set_reference(self, x_ref=None, u_ref=None):
         """New references (nx, N) / (nu, N) for every later step; None means zeros.  On a record controller one launch rewrites
         the part of the records that depends on them, enqueued on the solver's stream like a step; the arrays are copied before
-        this returns.  The carried active sets are kept: they only warm-start the next step (reset() forgets them)."""
+        this returns.  The carried active sets are kept: they only warm-start the next step (reset() forgets them).  Every call
+        raises reference_version by one: a plan taken before it no longer belongs to the controller's references (cost_grad and
+        model_grad read those)."""
         c = self._live()
+        self.reference_version += 1
         x_ref, u_ref = _ref_or_none(x_ref, self.nx, self.N), _ref_or_none(u_ref, self.nu, self.N)
         _lib.check(self._L.lqmpc_controller_set_reference(c, _ptr(x_ref), _ptr(u_ref)))
 

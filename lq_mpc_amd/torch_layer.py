@@ -5,6 +5,8 @@
     loss(u0, VN).backward()                              # x.grad through the local feedback law and the value gradient
     u0, VN = layer(x, A, B)                              # A, B fp64 device tensors, possibly requires_grad: the layer's new model
     loss(u0, VN).backward()                              # x.grad, and A.grad, B.grad through the model of every instance
+    u0, VN = layer(x, x_ref=xr, u_ref=ur)                # xr (nx, N), ur (nu, N) fp64 CPU tensors, possibly requires_grad: the new references
+    loss(u0, VN).backward()                              # x.grad, and xr.grad, ur.grad summed over the batch (with A, B: theirs too)
 
 Forward is one lqmpc_controller_step_sens_dev on the tensors' own pointers: the QP of every instance, then the post-pass that returns
 K_0 = d u_0 / d x and dV_N / d x on the face the plan ends on.  Backward is  grad_x = K_0' grad_u0 + dV_dx grad_VN, a torch einsum.
@@ -12,12 +14,19 @@ With A and B given, forward first replaces the controller's models in place (set
 states and the status; backward adds one lqmpc_controller_model_grad_dev (csrc/lqmpc_grad.hip: the adjoint LQ problem on the plan's
 face), which returns grad_A and grad_B.  That call reads the controller's own copies of the models, so backward raises if any
 set_model, through the layer or on layer.controller, came between the forward and its backward.
+With x_ref or u_ref given, forward first makes them the controller's references (set_reference; they are shared by the batch and
+host data, as everywhere in the library, so they are CPU tensors; one left out is zero); backward adds one
+lqmpc_controller_cost_grad_dev with reduce (csrc/lqmpc_cgrad.hip), which sums the gradient with respect to the references over the
+batch on the GPU, and copies the two small results to the host: that copy is the one wait for the host in the layer, and it happens
+on this path only.  Backward raises if a set_reference or a set_model came between the forward and its backward.
 The solver handle is created on torch's current stream (lqmpc_create_on_stream), so everything is ordered with the surrounding torch
-work on that stream and nothing waits for the host, in forward or in backward.  Use the layer under the stream it was made under.
+work on that stream and, but for that copy, nothing waits for the host, in forward or in backward.  Use the layer under the stream it
+was made under.
 
 The law of a box-constrained MPC is piecewise affine: the gradient is that of the critical region x lies in, exact inside it and
-one-sided on its border.  The model (A, B) is differentiated per instance; the weights, the box and the references are shared by the
-batch and are data, not differentiated.
+one-sided on its border.  The model (A, B) is differentiated per instance and the references for the batch as a whole.  The weights
+and the box are fixed when the controller is made, so the layer does not differentiate them: their gradients are those of
+BatchController.cost_grad and BatchSolver.cost_grad_batch.
 """
 import numpy as np
 import torch
@@ -92,9 +101,73 @@ class _MPCStepModel(torch.autograd.Function):
         return grad_x, grad_A, grad_B, None
 
 
+class _MPCStepRefs(torch.autograd.Function):
+    """the step under new references x_ref, u_ref (and, where given, new models A, B): differentiable in all of them and in x"""
+
+    @staticmethod
+    def forward(ctx, x, A, B, x_ref, u_ref, ctl):
+        nx, nu, N, Bsz = ctl.nx, ctl.nu, ctl.N, ctl.Bsz
+        if x.dtype != torch.float64 or not x.is_cuda or tuple(x.shape) != (nx, Bsz):
+            raise ValueError(f"x must be a float64 device tensor of shape ({nx}, {Bsz})")
+        for M, shape in ((x_ref, (nx, N)), (u_ref, (nu, N))):
+            if M is not None and (M.dtype != torch.float64 or M.is_cuda or tuple(M.shape) != shape):
+                raise ValueError(f"x_ref and u_ref must be float64 CPU tensors of shapes ({nx}, {N}) and ({nu}, {N})")
+        if A is not None:
+            for M, shape in ((A, (nx, nx, Bsz)), (B, (nx, nu, Bsz))):
+                if M.dtype != torch.float64 or not M.is_cuda or tuple(M.shape) != shape:
+                    raise ValueError(f"A and B must be float64 device tensors of shapes ({nx}, {nx}, {Bsz}) and ({nx}, {nu}, {Bsz})")
+            ctl.set_model(A.detach().contiguous(), B.detach().contiguous())
+        x = x.detach().contiguous()
+        ctl.set_reference(None if x_ref is None else x_ref.detach().contiguous().numpy(),
+                          None if u_ref is None else u_ref.detach().contiguous().numpy())
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=x.device)
+        u0, VN, K0, dV = new(nu, Bsz), new(Bsz), new(nu, nx, Bsz), new(nx, Bsz)
+        Up, Xp, st = new(nu, N, Bsz), new(nx, N + 1, Bsz), torch.empty(Bsz, dtype=torch.int32, device=x.device)
+        ctl.step_sens_dev(x, u0, K0, dV, dUplan=Up, dXplan=Xp, dVN=VN, dstatus=st)
+        ctx.save_for_backward(K0, dV, Up, Xp, st)
+        ctx.ctl, ctx.model_version, ctx.reference_version = ctl, ctl.model_version, ctl.reference_version
+        return u0, VN
+
+    @staticmethod
+    def backward(ctx, grad_u0, grad_VN):
+        K0, dV, Up, Xp, st = ctx.saved_tensors
+        ctl = ctx.ctl
+        if ctl.reference_version != ctx.reference_version:
+            raise RuntimeError("MPCLayer: the controller's references were replaced (set_reference) between this forward and its "
+                               "backward; the gradient would be that of other references")
+        if ctl.model_version != ctx.model_version:
+            raise RuntimeError("MPCLayer: the controller's models were replaced (set_model) between this forward and its backward; "
+                               "the gradient would be that of another model")
+        grad_x = None
+        if grad_u0 is not None:
+            grad_x = torch.einsum("kab,kb->ab", K0, grad_u0)
+        if grad_VN is not None:
+            g = dV * grad_VN.unsqueeze(0)
+            grad_x = g if grad_x is None else grad_x + g
+        grad_A = grad_B = grad_xr = grad_ur = None
+        if grad_u0 is None and grad_VN is None:
+            return grad_x, None, None, None, None, None
+        gu0 = None if grad_u0 is None else grad_u0.contiguous()
+        gVN = None if grad_VN is None else grad_VN.contiguous()
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            grad_A = torch.empty((ctl.nx, ctl.nx, ctl.Bsz), dtype=torch.float64, device=Xp.device)
+            grad_B = torch.empty((ctl.nx, ctl.nu, ctl.Bsz), dtype=torch.float64, device=Xp.device)
+            ctl.model_grad_dev(Up, Xp, grad_A, grad_B, dstatus=st, dgu0=gu0, dgVN=gVN)
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            g_xr = torch.empty((ctl.nx, ctl.N), dtype=torch.float64, device=Xp.device)
+            g_ur = torch.empty((ctl.nu, ctl.N), dtype=torch.float64, device=Xp.device)
+            ctl.cost_grad_dev(Up, Xp, dict(g_xref=g_xr, g_uref=g_ur), dstatus=st, dgu0=gu0, dgVN=gVN, reduce=True)
+            # the references live on the host: the one wait for the host in the layer
+            grad_xr = g_xr.cpu() if ctx.needs_input_grad[3] else None
+            grad_ur = g_ur.cpu() if ctx.needs_input_grad[4] else None
+        return grad_x, grad_A, grad_B, grad_xr, grad_ur, None
+
+
 class MPCLayer(torch.nn.Module):
     """u0, VN = MPCLayer(N, A, B, Q, R, P, lb, ub)(x) around a BatchController; options are the solver's (BatchSolver.set_options).
-    layer(x, A, B) steps under the models A, B (they become the controller's) and is differentiable in them as well."""
+    layer(x, A, B) steps under the models A, B (they become the controller's) and is differentiable in them as well;
+    layer(x, x_ref=xr, u_ref=ur), with or without A and B, steps under the references xr, ur (CPU tensors; they become the
+    controller's, one left out is zero) and is differentiable in them, summed over the batch."""
 
     def __init__(self, N, A, B, Q, R, P, lb, ub, x_ref=None, u_ref=None, **options):
         super().__init__()
@@ -104,11 +177,13 @@ class MPCLayer(torch.nn.Module):
             A, B = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(B, dtype=np.float64)
         self.controller = BatchController(self.solver, N, A, B, Q, R, P, lb, ub, x_ref, u_ref)
 
-    def forward(self, x, A=None, B=None):
-        if A is None and B is None:
-            return _MPCStep.apply(x, self.controller)
-        if A is None or B is None:
+    def forward(self, x, A=None, B=None, *, x_ref=None, u_ref=None):
+        if (A is None) != (B is None):
             raise ValueError("give both A and B, or neither")
+        if x_ref is not None or u_ref is not None:
+            return _MPCStepRefs.apply(x, A, B, x_ref, u_ref, self.controller)
+        if A is None:
+            return _MPCStep.apply(x, self.controller)
         return _MPCStepModel.apply(x, A, B, self.controller)
 
     def close(self):

@@ -1,0 +1,113 @@
+"""Dev tool: what the cost-gradient post-pass (lqmpc_cost_grad_kernel) costs, per instance and reduced on chip, beside the model-gradient
+post-pass (lqmpc_grad_kernel), which runs the same masked sweep, and beside the plan call; prints one JSON line.
+
+    python tools/cgrad_time.py [--cases C3 C4 C5 S3] [--calls 10] [--rounds 3] [--out FILE]
+
+Cases: C3 x 65 536, C4 x 262 144, C5 x 32 768 (the bench's default mix and batch sizes) through lqmpc_solve_plan_batch_dev /
+lqmpc_model_grad_batch_dev / lqmpc_cost_grad_batch_dev; S3 = a prepared controller at C3, step_plan_dev / model_grad_dev /
+cost_grad_dev (warm: the same state again).
+Variants per case: "plan" (Uplan and Xplan written), "grad" (the model-gradient call alone, with both cotangents and g_x0),
+"cgrad" (the cost-gradient call alone, per instance, all seven outputs), "cgrad_reduced" (the same, summed over the batch on chip).
+A sum over the per-instance outputs is not timed: it has to read output_bytes again, which the record carries, so "per instance
+plus a sum" costs more than "cgrad" alone, and the reduced call is the cheaper one wherever it is no slower than that.
+Every measurement is a process of its own (this one never opens the GPU): device-resident arrays, three warm-up rounds, then `calls`
+calls between lqmpc_timer_begin and lqmpc_timer_end.  The variants of a case alternate, `rounds` times, so that a drift of the clock
+shows as spread inside every variant and not as a difference between them.  Reported: every round's ms per call and the median."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+VARIANTS = ("plan", "grad", "cgrad", "cgrad_reduced")
+CASES = {"C3": 3, "C4": 4, "C5": 5, "S3": 3}
+KEYS = ("g_Q", "g_R", "g_P", "g_lb", "g_ub", "g_xref", "g_uref")
+
+
+def child(case, variant, calls):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from lq_mpc_amd import BatchController, BatchSolver, synth
+    from plan_time import Dev
+    s = BatchSolver(0)
+    b = synth.make_batch(CASES[case])
+    nx, nu, Bsz = b["B"].shape
+    N = b["N"]
+    w = (b["Q"], b["R"], b["P"], b["lb"], b["ub"])
+    dA, dB, dx = Dev(b["A"].shape, init=b["A"]), Dev(b["B"].shape, init=b["B"]), Dev(b["x0"].shape, init=b["x0"])
+    du, dv, dU, dX = Dev((nu, Bsz)), Dev(Bsz), Dev((nu, N, Bsz)), Dev((nx, N + 1, Bsz))
+    dst, dit = Dev(Bsz, np.int32), Dev(Bsz, np.int32)
+    s.reserve(nx, nu, N, Bsz)
+    ctl = BatchController(s, N, dA, dB, *w) if case.startswith("S") else None
+    plan = ((lambda: ctl.step_plan_dev(dx, du, dU, dX, dv, dst, dit)) if ctl else
+            (lambda: s.solve_plan_batch_dev(nx, nu, N, Bsz, dA, dB, *w, dx, du, dv, dU, dX, dst, dit)))
+    extra = {}
+    if variant == "plan":
+        go = plan
+    else:
+        plan()
+        rng = np.random.default_rng(5)
+        dgu, dgv = Dev((nu, Bsz), init=rng.standard_normal((nu, Bsz))), Dev(Bsz, init=rng.standard_normal(Bsz))
+        if variant == "grad":
+            dgA, dgB, dgx = Dev((nx, nx, Bsz)), Dev((nx, nu, Bsz)), Dev((nx, Bsz))
+            go = ((lambda: ctl.model_grad_dev(dU, dX, dgA, dgB, dst, dgu, dgv, dgx)) if ctl else
+                  (lambda: s.model_grad_batch_dev(nx, nu, N, Bsz, dA, dB, *w, dU, dX, dgA, dgB, dst, dgu, dgv, dgx)))
+        else:
+            red = variant == "cgrad_reduced"
+            shapes = ((nx, nx), (nu, nu), (nx, nx), (nu,), (nu,), (nx, N), (nu, N))
+            outs = {k: Dev(sh if red else sh + (Bsz,)) for k, sh in zip(KEYS, shapes)}
+            extra = dict(blocks=s.cost_grad_blocks(nx, nu, N, Bsz, red), output_bytes=int(sum(o.nbytes for o in outs.values())))
+            go = ((lambda: ctl.cost_grad_dev(dU, dX, outs, dst, dgu, dgv, reduce=red)) if ctl else
+                  (lambda: s.cost_grad_batch_dev(nx, nu, N, Bsz, dA, dB, *w, dU, dX, outs, dst, dgu, dgv, reduce=red)))
+    for _ in range(3):
+        go()
+    s.timer_begin()
+    for _ in range(calls):
+        go()
+    ms = s.timer_end() / calls
+    st = dst.numpy()
+    print(json.dumps(dict(ms=ms, kernel=s.last_kernel(), shape=[nx, nu, N], Bsz=int(Bsz), status_nonzero=int((st != 0).sum()), **extra)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", nargs="*", default=list(CASES))
+    ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", nargs=2, default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child[0], a.child[1], a.calls)
+    out = {"tool": "cgrad_time", "calls": a.calls, "rounds": a.rounds, "cases": {}}
+    for case in a.cases:
+        rec = {v: [] for v in VARIANTS}
+        info, extra = {}, {}
+        for _ in range(a.rounds):
+            for v in VARIANTS:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", case, v, "--calls", str(a.calls)],
+                                   capture_output=True, text=True, timeout=300)
+                if r.returncode != 0:
+                    raise SystemExit(f"{case} {v}: exit {r.returncode}\n{r.stdout[-2000:]}{r.stderr[-4000:]}")
+                info = json.loads(r.stdout.strip().splitlines()[-1])
+                rec[v].append(round(info.pop("ms"), 5))
+                for k in ("blocks", "output_bytes"):
+                    if k in info:
+                        extra[f"{v}_{k}"] = info.pop(k)
+        med = {v: round(float(np.median(rec[v])), 5) for v in VARIANTS}
+        out["cases"][case] = dict(info, **extra, ms=rec, median_ms=med, grad_post_pass_ms=med["grad"], cgrad_post_pass_ms=med["cgrad"],
+                                  cgrad_reduced_ms=med["cgrad_reduced"], cgrad_over_grad=round(med["cgrad"] / med["grad"], 3),
+                                  reduced_over_per_instance=round(med["cgrad_reduced"] / med["cgrad"], 3))
+        print(case, out["cases"][case], file=sys.stderr, flush=True)
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
