@@ -14,7 +14,7 @@ l, l~ of tests/grad_ref.py, r_i = 2 R d_i + B'l_{i+1} and r~_i = 2 R u~_i + B'l~
                 stage gradients from the condensed problem itself, r = 2 (H U + g) and r~ = 2 H U~ (no costate, no Riccati sweep).
   face_loss()   long double: w'u_0 + gam V at the optimum of a FIXED face for overridden weights, references and bounds; the entries
                 held at a bound move with the bound.  What the central differences of tests/test_cgrad_cpu.py differentiate.
-  adjoint()     the fp64 numpy restatement of what lqmpc_cost_grad_kernel computes: the masked Riccati sweep, one forward roll, the
+  adjoint()     the numpy restatement (fp64; long double on request) of what lqmpc_cost_grad_kernel computes: the masked Riccati sweep, one forward roll, the
                 two costate recursions and the sums.
 """
 import numpy as np
@@ -135,41 +135,41 @@ def face_loss(p, kw, x0, side, w, gam, **over):
     return np.einsum("kb,bk->b", np.asarray(w, dtype=LD), U[:, :nu]) + np.asarray(gam, dtype=LD) * ex.value(H, g, c, U)
 
 
-def adjoint(N, A, B, Q, R, P, side, X, U, w, gam, x_ref=None, u_ref=None):
-    """fp64 numpy, the algebra of lqmpc_cost_grad_kernel: side (nu, N, Bsz) the face, X (nx, N + 1, Bsz) and U (nu, N, Bsz) the plan,
-    w (nu, Bsz), gam (Bsz,).  Returns the seven outputs of KEYS.
+def adjoint(N, A, B, Q, R, P, side, X, U, w, gam, x_ref=None, u_ref=None, dtype=np.float64, chol=False, stats=None):
+    """numpy, the algebra of lqmpc_cost_grad_kernel: side (nu, N, Bsz) the face, X (nx, N + 1, Bsz) and U (nu, N, Bsz) the plan,
+    w (nu, Bsz), gam (Bsz,).  Returns the seven outputs of KEYS.  dtype, chol, stats: see sens_ref.stage_solver (fp64 and LU by default).
         the sweep of sens_ref.masked_sweep, keeping K_j of every stage and Re_0
         u~_0 = 1/2 f_0 Re_0^-1 f_0 w,  x~_0 = 0;  j = 0 .. N-1: u~_j = -K_j x~_j (j > 0),  x~_{j+1} = A x~_j + B u~_j
         the costates l (of X, with references) and l~ (of x~, without), r_i = 2 R d_i + B'l_{i+1}, r~_i = 2 R u~_i + B'l~_{i+1}"""
-    f64 = lambda a: np.asarray(a, dtype=np.float64)
-    Ab, Bb = np.moveaxis(f64(A), -1, 0), np.moveaxis(f64(B), -1, 0)
-    Q, R, P = f64(Q), f64(R), f64(P)
+    cast = lambda a: np.asarray(a, dtype=dtype)
+    Ab, Bb = np.moveaxis(cast(A), -1, 0), np.moveaxis(cast(B), -1, 0)
+    Q, R, P = cast(Q), cast(R), cast(P)
     Bsz, nx, nu = Bb.shape
     free = side == 0
     S = np.broadcast_to(P, (Bsz, nx, nx)).copy()
     Ks = [None] * N
-    eye = np.eye(nu)
-    Re = None
+    eye = np.eye(nu, dtype=dtype)
+    solve = None
     for j in range(N - 1, -1, -1):
-        f = free[:, j, :].T.astype(np.float64)
+        f = free[:, j, :].T.astype(dtype)
         Bj = Bb * f[:, None, :]
-        Rj = f[:, :, None] * R[None] * f[:, None, :] + eye[None] * (1.0 - f)[:, :, None]
+        Rj = f[:, :, None] * R[None] * f[:, None, :] + eye[None] * (1 - f)[:, :, None]
         BtS = np.einsum("bji,bjk->bik", Bj, S)
-        Re = Rj + BtS @ Bj
-        Ks[j] = np.linalg.solve(Re, BtS @ Ab)
+        solve = sr.stage_solver(Rj + BtS @ Bj, dtype, chol, stats)
+        Ks[j] = solve(BtS @ Ab)
         S = Q[None] + np.einsum("bji,bjk->bik", Ab, S @ (Ab - Bj @ Ks[j]))
-    f0 = free[:, 0, :].T.astype(np.float64)
-    wb, gb = f64(w).T, f64(gam)
-    Xt, Ut = np.zeros((Bsz, N + 1, nx)), np.zeros((Bsz, N, nu))
-    Ut[:, 0] = 0.5 * f0 * np.linalg.solve(Re, (f0 * wb)[:, :, None])[:, :, 0]
+    f0 = free[:, 0, :].T.astype(dtype)
+    wb, gb = cast(w).T, cast(gam)
+    Xt, Ut = np.zeros((Bsz, N + 1, nx), dtype=dtype), np.zeros((Bsz, N, nu), dtype=dtype)
+    Ut[:, 0] = f0 * solve((f0 * wb)[:, :, None])[:, :, 0] / 2
     for j in range(N):
         if j:
             Ut[:, j] = -np.einsum("bki,bi->bk", Ks[j], Xt[:, j])
         Xt[:, j + 1] = np.einsum("bij,bj->bi", Ab, Xt[:, j]) + np.einsum("bik,bk->bi", Bb, Ut[:, j])
-    xr, ur = _refs(dict(x_ref=x_ref, u_ref=u_ref), nx, nu, N, np.float64)
-    Xb, Ub = np.moveaxis(f64(X), -1, 0).transpose(0, 2, 1), np.moveaxis(f64(U), -1, 0).transpose(0, 2, 1)
+    xr, ur = _refs(dict(x_ref=x_ref, u_ref=u_ref), nx, nu, N, dtype)
+    Xb, Ub = np.moveaxis(cast(X), -1, 0).transpose(0, 2, 1), np.moveaxis(cast(U), -1, 0).transpose(0, 2, 1)
     lam = gr._costates(N, Ab, Q, P, Xb, xr)
-    lamt = gr._costates(N, Ab, Q, P, Xt, np.zeros((N, nx)))
+    lamt = gr._costates(N, Ab, Q, P, Xt, np.zeros((N, nx), dtype=dtype))
     r = np.stack([2 * np.einsum("kl,bl->bk", R, Ub[:, i] - ur[i]) + np.einsum("bmk,bm->bk", Bb, lam[i + 1]) for i in range(N)], axis=1)
     rt = np.stack([2 * np.einsum("kl,bl->bk", R, Ut[:, i]) + np.einsum("bmk,bm->bk", Bb, lamt[i + 1]) for i in range(N)], axis=1)
     return _sums(N, Q, R, P, Xb, Ub, Xt, Ut, xr, ur, r, rt, np.moveaxis(side, -1, 0).transpose(0, 2, 1), wb, gb)

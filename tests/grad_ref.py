@@ -11,7 +11,7 @@ matrices A and B of every instance, on the face the plan reports (DESIGN.md sect
                 No Riccati sweep anywhere.
   face_loss()   long double: w'u_0 + gam V at the optimum of a FIXED face, U_F = -H_FF^-1 (g_F + H_FA U_A), for any model; what the
                 central differences of tests/test_grad_cpu.py differentiate.
-  adjoint()     the fp64 numpy restatement of what lqmpc_grad_kernel computes: the masked Riccati sweep of sens_ref.masked_sweep
+  adjoint()     the numpy restatement (fp64; long double on request) of what lqmpc_grad_kernel computes: the masked Riccati sweep of sens_ref.masked_sweep
                 (the same recursion, keeping K_j and Re_0), one forward roll, one backward pass.
   cotangents()  seeded random w and gam for a batch.
 """
@@ -109,37 +109,38 @@ def face_loss(p, kw, x0, free, U_bound, w, gam, A=None, B=None):
     return np.einsum("kb,bk->b", np.asarray(w, dtype=LD), U[:, :nu]) + np.asarray(gam, dtype=LD) * ex.value(H, g, c, U)
 
 
-def adjoint(N, A, B, Q, R, P, free, X, U, w, gam, x_ref=None):
-    """fp64 numpy, the algebra of lqmpc_grad_kernel: free (nu, N, Bsz) the face, X (nx, N + 1, Bsz) and U (nu, N, Bsz) the plan,
-    w (nu, Bsz), gam (Bsz,).  Returns {'g_A', 'g_B', 'g_x0'}.
+def adjoint(N, A, B, Q, R, P, free, X, U, w, gam, x_ref=None, dtype=np.float64, chol=False, stats=None):
+    """numpy, the algebra of lqmpc_grad_kernel: free (nu, N, Bsz) the face, X (nx, N + 1, Bsz) and U (nu, N, Bsz) the plan,
+    w (nu, Bsz), gam (Bsz,).  Returns {'g_A', 'g_B', 'g_x0'}.  dtype, chol, stats: see sens_ref.stage_solver (fp64 and LU by default).
         the sweep of sens_ref.masked_sweep, keeping K_j of every stage and Re_0
         u~_0 = 1/2 f_0 Re_0^-1 f_0 w,  x~_0 = 0;  j = 0 .. N-1: u~_j = -K_j x~_j (j > 0),  x~_{j+1} = A x~_j + B u~_j
         the costates l (of X, with references) and l~ (of x~, without), backwards together, and the sums of the module docstring"""
-    Ab, Bb = np.moveaxis(np.asarray(A, dtype=np.float64), -1, 0), np.moveaxis(np.asarray(B, dtype=np.float64), -1, 0)
+    cast = lambda a: np.asarray(a, dtype=dtype)
+    Ab, Bb = np.moveaxis(cast(A), -1, 0), np.moveaxis(cast(B), -1, 0)
+    Q, R, P = cast(Q), cast(R), cast(P)
     Bsz, nx, nu = Bb.shape
     S = np.broadcast_to(P, (Bsz, nx, nx)).copy()
     Ks = [None] * N
-    eye = np.eye(nu)
-    Re = None
+    eye = np.eye(nu, dtype=dtype)
+    solve = None
     for j in range(N - 1, -1, -1):
-        f = free[:, j, :].T.astype(np.float64)
+        f = free[:, j, :].T.astype(dtype)
         Bj = Bb * f[:, None, :]
-        Rj = f[:, :, None] * R[None] * f[:, None, :] + eye[None] * (1.0 - f)[:, :, None]
+        Rj = f[:, :, None] * R[None] * f[:, None, :] + eye[None] * (1 - f)[:, :, None]
         BtS = np.einsum("bji,bjk->bik", Bj, S)
-        Re = Rj + BtS @ Bj
-        Ks[j] = np.linalg.solve(Re, BtS @ Ab)
+        solve = sr.stage_solver(Rj + BtS @ Bj, dtype, chol, stats)
+        Ks[j] = solve(BtS @ Ab)
         S = Q[None] + np.einsum("bji,bjk->bik", Ab, S @ (Ab - Bj @ Ks[j]))
-    f0 = free[:, 0, :].T.astype(np.float64)
-    Xt, Ut = np.zeros((Bsz, N + 1, nx)), np.zeros((Bsz, N, nu))
-    Ut[:, 0] = 0.5 * f0 * np.linalg.solve(Re, (f0 * np.asarray(w, dtype=np.float64).T)[:, :, None])[:, :, 0]
+    f0 = free[:, 0, :].T.astype(dtype)
+    Xt, Ut = np.zeros((Bsz, N + 1, nx), dtype=dtype), np.zeros((Bsz, N, nu), dtype=dtype)
+    Ut[:, 0] = f0 * solve((f0 * cast(w).T)[:, :, None])[:, :, 0] / 2
     for j in range(N):
         if j:
             Ut[:, j] = -np.einsum("bki,bi->bk", Ks[j], Xt[:, j])
         Xt[:, j + 1] = np.einsum("bij,bj->bi", Ab, Xt[:, j]) + np.einsum("bik,bk->bi", Bb, Ut[:, j])
-    xr = np.zeros((N, nx)) if x_ref is None else np.asarray(x_ref, dtype=np.float64).T
-    Xb, Ub = np.moveaxis(np.asarray(X, dtype=np.float64), -1, 0).transpose(0, 2, 1), np.moveaxis(np.asarray(U, dtype=np.float64), -1, 0).transpose(0, 2, 1)
-    Q, P = np.asarray(Q, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    xr = np.zeros((N, nx), dtype=dtype) if x_ref is None else cast(x_ref).T
+    Xb, Ub = np.moveaxis(cast(X), -1, 0).transpose(0, 2, 1), np.moveaxis(cast(U), -1, 0).transpose(0, 2, 1)
     lam = _costates(N, Ab, Q, P, Xb, xr)
-    lamt = _costates(N, Ab, Q, P, Xt, np.zeros((N, nx)))
-    gA, gB, gx = _sums(N, Ab, Q, lam, lamt, Xb, Ub, Xt, Ut, np.asarray(gam, dtype=np.float64))
+    lamt = _costates(N, Ab, Q, P, Xt, np.zeros((N, nx), dtype=dtype))
+    gA, gB, gx = _sums(N, Ab, Q, lam, lamt, Xb, Ub, Xt, Ut, cast(gam))
     return dict(g_A=gA, g_B=gB, g_x0=gx)

@@ -7,7 +7,11 @@
                       dVdx = the central difference with step 1 of value(H, g(x), c(x), U*) at fixed U* (exact: V is quadratic in x)
   masked_sweep(), costate()
                       an fp64 numpy restatement of what lqmpc_sens_kernel computes: one backward Riccati sweep with a free mask per
-                      stage and one forward product; one costate recursion over the predicted states
+                      stage and one forward product; one costate recursion over the predicted states.  With dtype = long double
+                      the same operation as a reference (tests/postpass_hard.py)
+  chol_factor(), chol_apply(), stage_solver()
+                      how a stage matrix Re is solved with: numpy.linalg.solve by default (what the restatements have always
+                      used, bit for bit), the kernels' own Cholesky on request, oracle/exact.py's in long double
 """
 import numpy as np
 
@@ -144,13 +148,20 @@ def reference(p, kw, x0, U_plan):
         e[a] = 1
         Fx[:, :, a] = cond(e)[0] - g0
         dV[a] = (ex.value(H, *cond(x0l + e), Us) - ex.value(H, *cond(x0l - e), Us)) / 2
-    K = np.zeros((Bsz, n, nx), dtype=LD)
-    for b in range(Bsz):
+    K = gain_on_face(H, Fx, Ffree)
+    return dict(K_plan=K.reshape(Bsz, N, nu, nx).transpose(2, 1, 3, 0), dV_dx=dV, free=free, U=cert["U"], ok=cert["ok"])
+
+
+def gain_on_face(H, Fx, Ffree):
+    """(Bsz, n, nx) long double: K[F] = -H_FF^-1 Fx[F] on the face Ffree (Bsz, n) bool, time-major as exact.condense; zero elsewhere.
+    It depends on the face alone, not on the plan that has it."""
+    K = np.zeros(Fx.shape, dtype=LD)
+    for b in range(Fx.shape[0]):
         F = np.flatnonzero(Ffree[b])
         if F.size:
             L = ex.cholesky(H[b][np.ix_(F, F)])
             K[b, F, :] = -ex.chol_solve(L[None], Fx[b, F, :].T).T
-    return dict(K_plan=K.reshape(Bsz, N, nu, nx).transpose(2, 1, 3, 0), dV_dx=dV, free=free, U=cert["U"], ok=cert["ok"])
+    return K
 
 
 def oracle_face(p, kw, x0, U_oracle):
@@ -179,7 +190,7 @@ def rel_err(got, ref, axes):
     return np.asarray(np.max(np.abs(got - ref), axis=axes) / np.maximum(np.max(np.abs(ref), axis=axes), 1), dtype=np.float64)
 
 
-# ---------------- fp64 numpy restatement of the kernel's algebra ----------------
+# ---------------- numpy restatement of the kernel's algebra: fp64, or long double as a reference of the same operation ----------------
 def face_bits(U, lb, ub):
     """free mask of an fp64 plan by the rule of include/lqmpc.h: an entry is on a bound when it equals, bit for bit, lb, ub,
     c - h or c + h with c = (ub + lb) / 2, h = (ub - lb) / 2"""
@@ -188,38 +199,83 @@ def face_bits(U, lb, ub):
     return ~((U == lb) | (U == ub) | (U == c - h) | (U == c + h))
 
 
-def masked_sweep(N, A, B, Q, R, P, free):
+def chol_factor(Re, stats=None):
+    """The factor the post-pass kernels form of a stack of stage matrices Re (Bsz, m, m), in Re's own dtype: Cholesky column by column
+    from the LOWER triangle (the upper one is never read), (L, Di) with L below the diagonal and Di the reciprocals of the factor's
+    diagonal.  A pivot that is not positive gives NaN, as in the kernels.  stats, a dict: 'pivot' takes the smallest pivot relative to
+    its diagonal entry, 'positive' whether every pivot was positive."""
+    m = Re.shape[-1]
+    L, Di = np.zeros_like(Re), np.zeros(Re.shape[:-1], dtype=Re.dtype)
+    for q in range(m):
+        dq = Re[:, q, q] - np.sum(L[:, q, :q] * L[:, q, :q], axis=-1)
+        if stats is not None:
+            stats["pivot"] = min(stats.get("pivot", np.inf), float(np.min(dq / Re[:, q, q])))
+            stats["positive"] = stats.get("positive", True) and bool(np.all(dq > 0))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            Di[:, q] = 1 / np.sqrt(dq)
+        L[:, q + 1:, q] = (Re[:, q + 1:, q] - np.einsum("bik,bk->bi", L[:, q + 1:, :q], L[:, q, :q])) * Di[:, q, None]
+    return L, Di
+
+
+def chol_apply(L, Di, G):
+    """(L L')^-1 G for right-hand sides G (Bsz, m, c): the two substitutions of the kernels, multiplying by the reciprocal diagonal"""
+    Y = np.array(G)
+    m = L.shape[-1]
+    for k in range(m):
+        Y[:, k] = (Y[:, k] - np.einsum("bm,bmc->bc", L[:, k, :k], Y[:, :k])) * Di[:, k, None]
+    for k in range(m - 1, -1, -1):
+        Y[:, k] = (Y[:, k] - np.einsum("bm,bmc->bc", L[:, k + 1:, k], Y[:, k + 1:])) * Di[:, k, None]
+    return Y
+
+
+def stage_solver(Re, dtype=np.float64, chol=False, stats=None):
+    """G (Bsz, m, c) -> Re^-1 G.  The default is numpy.linalg.solve (LU), what the restatements have always used; chol = True factors
+    as the kernels do (chol_factor, chol_apply); long double goes through exact.cholesky / exact.chol_solve, numpy.linalg having no
+    long double."""
+    if np.dtype(dtype) == np.dtype(LD) and np.dtype(LD) != np.dtype(np.float64):
+        L = ex.cholesky(Re)
+        return lambda G: np.swapaxes(ex.chol_solve(L[:, None], np.swapaxes(G, 1, 2)), 1, 2)
+    if chol:
+        L, Di = chol_factor(Re, stats)
+        return lambda G: chol_apply(L, Di, G)
+    return lambda G: np.linalg.solve(Re, G)
+
+
+def masked_sweep(N, A, B, Q, R, P, free, dtype=np.float64, chol=False, stats=None):
     """K_plan (nu, N, nx, Bsz) = d u_i / d x0 on the face `free` (nu, N, Bsz):
         B_j = B diag(f_j), R_j = diag(f_j) R diag(f_j) + diag(1 - f_j)
         S = P; j = N-1..0: Re = R_j + B_j'S B_j, K_j = Re^-1 B_j'S A, Acl_j = A - B_j K_j, S <- Q + A'S Acl_j
-        Pi_0 = I; j = 0..N-1: du_j/dx0 = -K_j Pi_j, Pi_{j+1} = Acl_j Pi_j"""
-    Ab, Bb = np.moveaxis(np.asarray(A, dtype=np.float64), -1, 0), np.moveaxis(np.asarray(B, dtype=np.float64), -1, 0)
+        Pi_0 = I; j = 0..N-1: du_j/dx0 = -K_j Pi_j, Pi_{j+1} = Acl_j Pi_j
+    dtype, chol, stats: see stage_solver; rows of fixed inputs are exact zeros either way"""
+    Ab, Bb = np.moveaxis(np.asarray(A, dtype=dtype), -1, 0), np.moveaxis(np.asarray(B, dtype=dtype), -1, 0)
+    Q, R, P = (np.asarray(M, dtype=dtype) for M in (Q, R, P))
     Bsz, nx, nu = Bb.shape
     S = np.broadcast_to(P, (Bsz, nx, nx)).copy()
     Ks, Acl = [None] * N, [None] * N
-    eye = np.eye(nu)
+    eye = np.eye(nu, dtype=dtype)
     for j in range(N - 1, -1, -1):
-        f = free[:, j, :].T.astype(np.float64)                                          # (Bsz, nu)
+        f = free[:, j, :].T.astype(dtype)                                               # (Bsz, nu)
         Bj = Bb * f[:, None, :]
-        Rj = f[:, :, None] * R[None] * f[:, None, :] + eye[None] * (1.0 - f)[:, :, None]
+        Rj = f[:, :, None] * R[None] * f[:, None, :] + eye[None] * (1 - f)[:, :, None]
         BtS = np.einsum("bji,bjk->bik", Bj, S)
-        Ks[j] = np.linalg.solve(Rj + BtS @ Bj, BtS @ Ab)
+        Ks[j] = stage_solver(Rj + BtS @ Bj, dtype, chol, stats)(BtS @ Ab)
         Acl[j] = Ab - Bj @ Ks[j]
         S = Q[None] + np.einsum("bji,bjk->bik", Ab, S @ Acl[j])
-    Pi = np.broadcast_to(np.eye(nx), (Bsz, nx, nx)).copy()
-    out = np.zeros((nu, N, nx, Bsz))
+    Pi = np.broadcast_to(np.eye(nx, dtype=dtype), (Bsz, nx, nx)).copy()
+    out = np.zeros((nu, N, nx, Bsz), dtype=dtype)
     for j in range(N):
         out[:, j] = np.moveaxis(-Ks[j] @ Pi, 0, -1)
         Pi = Acl[j] @ Pi
     return out
 
 
-def costate(N, A, Q, P, X, x_ref=None):
+def costate(N, A, Q, P, X, x_ref=None, dtype=np.float64):
     """dV_N/dx0 (nx, Bsz) from the predicted states X (nx, N + 1, Bsz):
         l_N = 2 P (x_N - xref_{N-1}), l_i = 2 Q (x_i - xref_{i-1}) + A'l_{i+1}, dV/dx0 = 2 Q x0 + A'l_1"""
     nx = X.shape[0]
-    xr = np.zeros((nx, N)) if x_ref is None else np.asarray(x_ref, dtype=np.float64)
-    lam = 2.0 * P @ (X[:, N] - xr[:, N - 1][:, None])
+    A, Q, P, X = (np.asarray(M, dtype=dtype) for M in (A, Q, P, X))
+    xr = np.zeros((nx, N), dtype=dtype) if x_ref is None else np.asarray(x_ref, dtype=dtype)
+    lam = 2 * P @ (X[:, N] - xr[:, N - 1][:, None])
     for i in range(N - 1, 0, -1):
-        lam = 2.0 * Q @ (X[:, i] - xr[:, i - 1][:, None]) + np.einsum("mab,mb->ab", A, lam)
-    return 2.0 * Q @ X[:, 0] + np.einsum("mab,mb->ab", A, lam)
+        lam = 2 * Q @ (X[:, i] - xr[:, i - 1][:, None]) + np.einsum("mab,mb->ab", A, lam)
+    return 2 * Q @ X[:, 0] + np.einsum("mab,mb->ab", A, lam)
