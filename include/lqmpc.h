@@ -344,6 +344,48 @@ int lqmpc_cost_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bs
                               int64_t *dnskipped);
 int64_t lqmpc_cost_grad_blocks(int nx, int nu, int N, int64_t Bsz, int reduce);
 
+/* ---- the gradient of a loss on the whole plan -- every u_i, every x_i and V_N -- with respect to the model and the given state ----
+ * Given what a plan or sens call wrote (Uplan, Xplan, status; status may be NULL = all 0) and the cotangents, laid out like what they
+ * belong to:
+ *     gUplan[(k*N + i)*Bsz + b]     = d loss / d u_i[k]   i = 0..N-1
+ *     gXplan[(a*(N+1) + i)*Bsz + b] = d loss / d x_i[a]   i = 0..N     (row i = 0 acts on the given state and goes to gx0 as it is)
+ *     gVN[b]                        = d loss / d V_N
+ * any of them may be NULL = zero, not all three, the outputs are those of lqmpc_model_grad_batch, instance-minor like A and B:
+ *     gA[(a*nx + c)*Bsz + b]  = d loss / d A[a][c] of instance b
+ *     gB[(a*nu + k)*Bsz + b]  = d loss / d B[a][k] of instance b
+ *     gx0[a*Bsz + b]          = d loss / d x0[a]
+ * Any output may be NULL, not all; gA and gB are independent of each other.  All cotangents NULL, all outputs NULL, a NULL handle,
+ * model or plan: LQMPC_ERR_BAD_ARG before anything is enqueued.  The call is the post-pass alone -- one launch of
+ * lqmpc_plan_grad_kernel on the handle's stream, no solve: the cotangents are only known at backward time -- so A, B, the weights, the
+ * box and the references must be those of the call that wrote the plan; lqmpc_last_kernel is left naming the solve kernel.
+ * The gradient is that of the FACE THE PLAN REPORTS, by the rule of lqmpc_solve_sens_batch: an entry of Uplan is on a bound when it
+ * equals, bit for bit, lb_k, ub_k, c_k - h_k or c_k + h_k (no tolerance), the inputs on a bound do not move and the others are free.
+ * On that face the gradient is the adjoint of an equality-constrained LQ problem with a linear term at every stage: one backward
+ * Riccati sweep with a free mask per stage and an affine part beside it, one forward roll of N steps, two costate recursions and 2N
+ * rank-1 updates, never an n x n matrix.  The gVN part follows from the envelope theorem and holds on every face.  At the border of
+ * two critical regions (a weakly active bound) the gradient is one-sided: the call returns that of the face the plan reports.
+ * An entry of gUplan that belongs to an input on a bound changes no bit of any output, whatever it holds.  An instance whose
+ * cotangents are all 0.0 gets exact 0.0 everywhere; an instance with status 2 gets NaN in gA, gB and gx0.  With gUplan zero behind
+ * stage 0 and gXplan NULL the outputs are those of lqmpc_model_grad_batch to rounding.  A shape whose LDS image would not fit 160 KiB
+ * is refused with LQMPC_ERR_UNSUPPORTED before anything is enqueued (none within the build limits: the largest, (16, 2, 64), takes
+ * 153 568 bytes). */
+int lqmpc_plan_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                          const double *A, const double *B,
+                          const double *Q, const double *R, const double *P,
+                          const double *lb, const double *ub,
+                          const double *x_ref, const double *u_ref,
+                          const double *Uplan, const double *Xplan, const int32_t *status,
+                          const double *gUplan, const double *gXplan, const double *gVN,
+                          double *gA, double *gB, double *gx0);
+int lqmpc_plan_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                              const double *dA, const double *dB,
+                              const double *Q, const double *R, const double *P,
+                              const double *lb, const double *ub,
+                              const double *x_ref, const double *u_ref,
+                              const double *dUplan, const double *dXplan, const int32_t *dstatus,
+                              const double *dgUplan, const double *dgXplan, const double *dgVN,
+                              double *dgA, double *dgB, double *dgx0);
+
 /* ---- LQ_MPC_Simulator.simulate, batched (utils_class.py:245-285) ----
  * The model (A,B) drives the QP, the plant (A_true,B_true) drives the state.
  * true_per_instance == 0: A_true/B_true are single HOST matrices shared by the batch
@@ -480,6 +522,8 @@ int lqmpc_bounds_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
  *   the next step is bit for bit what it is without the call.
  * cost_grad: lqmpc_cost_grad_batch likewise, on the controller's models, weights, box and current references (those of the last
  *   set_reference).  Read-only on the controller as well.
+ * plan_grad: lqmpc_plan_grad_batch likewise, on the controller's own copies of A and B (on workgroup records the heads of the
+ *   records) and its current references: record, workgroup and pass-through controllers alike.  Read-only on the controller.
  * reset: forget the stored active sets (the next step starts cold).  bytes: HBM held by the controller.  kernel: the kernel its
  *   steps launch (contains "ctl"), or for a pass-through controller the kernel its last step ran.  destroy: NULL is fine.
  * set_reference: new references for every later step, x_ref (nx x N) and u_ref (nu x N) HOST, row-major, NULL = zeros -- for a loop
@@ -553,6 +597,11 @@ int lqmpc_controller_cost_grad_dev(lqmpc_controller *c, const double *dUplan, co
                                    const double *dgu0, const double *dgVN, int reduce,
                                    double *dgQ, double *dgR, double *dgP, double *dglb, double *dgub, double *dgxref, double *dguref,
                                    int64_t *dnskipped);
+int lqmpc_controller_plan_grad(lqmpc_controller *c, const double *Uplan, const double *Xplan, const int32_t *status,
+                               const double *gUplan, const double *gXplan, const double *gVN, double *gA, double *gB, double *gx0);
+int lqmpc_controller_plan_grad_dev(lqmpc_controller *c, const double *dUplan, const double *dXplan, const int32_t *dstatus,
+                                   const double *dgUplan, const double *dgXplan, const double *dgVN,
+                                   double *dgA, double *dgB, double *dgx0);
 int lqmpc_controller_rollout(lqmpc_controller *c, int T, const double *x0,
                              const double *A_true, const double *B_true, int true_per_instance,
                              double *JT, double *X, double *U, int32_t *status, int32_t *iters);

@@ -40,6 +40,7 @@ EXPORTS = [
     "lqmpc_model_grad_batch", "lqmpc_model_grad_batch_dev", "lqmpc_controller_model_grad", "lqmpc_controller_model_grad_dev",
     "lqmpc_cost_grad_batch", "lqmpc_cost_grad_batch_dev", "lqmpc_controller_cost_grad", "lqmpc_controller_cost_grad_dev",
     "lqmpc_cost_grad_blocks",
+    "lqmpc_plan_grad_batch", "lqmpc_plan_grad_batch_dev", "lqmpc_controller_plan_grad", "lqmpc_controller_plan_grad_dev",
 ]
 
 
@@ -107,6 +108,8 @@ def lib():
     L.lqmpc_cost_grad_batch_dev.argtypes = dims + [P] * 14 + [ctypes.c_int] + [P] * 8
     L.lqmpc_cost_grad_blocks.argtypes = [ctypes.c_int] * 3 + [ctypes.c_int64, ctypes.c_int]
     L.lqmpc_cost_grad_blocks.restype = ctypes.c_int64
+    L.lqmpc_plan_grad_batch.argtypes = dims + [P] * 18
+    L.lqmpc_plan_grad_batch_dev.argtypes = dims + [P] * 18
     roll_args = dims + [ctypes.c_int] + [P] * 10 + [ctypes.c_int] + [P] * 7
     L.lqmpc_rollout_batch.argtypes = roll_args
     L.lqmpc_rollout_batch_dev.argtypes = roll_args
@@ -139,6 +142,8 @@ def lib():
     L.lqmpc_controller_model_grad_dev.argtypes = [_H] + [P] * 8
     L.lqmpc_controller_cost_grad.argtypes = [_H] + [P] * 5 + [ctypes.c_int] + [P] * 8
     L.lqmpc_controller_cost_grad_dev.argtypes = [_H] + [P] * 5 + [ctypes.c_int] + [P] * 8
+    L.lqmpc_controller_plan_grad.argtypes = [_H] + [P] * 9
+    L.lqmpc_controller_plan_grad_dev.argtypes = [_H] + [P] * 9
     ctl_roll_args = [_H, ctypes.c_int, P, P, P, ctypes.c_int] + [P] * 5
     L.lqmpc_controller_rollout.argtypes = ctl_roll_args
     L.lqmpc_controller_rollout_dev.argtypes = ctl_roll_args

@@ -782,6 +782,41 @@ static int cgrad_launch(lqmpc_handle *h, const Call &c, lqmpc::CGradParams &g)
     return 0;
 }
 
+// The plan-gradient calls (lqmpc_plan_grad_batch_dev, lqmpc_controller_plan_grad_dev): the checks, the shared block of `c` (the one the
+// plan call before it uploaded, so nothing is copied again) and one launch of lqmpc_plan_grad_kernel.  No solve, no plan: nothing is
+// routed or compiled, and lqmpc_last_kernel is left naming the solve kernel.
+static int pgrad_check(const void *owner, const Call *c, int nx, int nu, int N, const double *Uplan, const double *Xplan, const double *gU,
+                       const double *gX, const double *gVN, const double *gA, const double *gB, const double *gx0)
+{
+    if (!owner || !Uplan || !Xplan) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (!gU && !gX && !gVN) return fail(LQMPC_ERR_BAD_ARG, "gUplan, gXplan and gVN are all NULL: there is no cotangent");
+    if (!gA && !gB && !gx0) return fail(LQMPC_ERR_BAD_ARG, "every output is NULL");
+    if (c) {                                                    // (a controller's own data passed these checks when it was made)
+        const int rc = check_call(*c);
+        if (rc) return rc;
+    }
+    if (!lqmpc::pgrad_fits(nx, nu, N)) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "lqmpc_plan_grad_kernel needs %zu bytes of LDS at (%d,%d,%d): over 160 KiB", lqmpc::pgrad_lds_bytes(nx, nu, N),
+                 nx, nu, N);
+        return fail(LQMPC_ERR_UNSUPPORTED, buf);
+    }
+    return 0;
+}
+
+static int pgrad_launch(lqmpc_handle *h, const Call *check, const Call &c, lqmpc::PGradParams &g)
+{
+    int rc = pgrad_check(h, check, c.nx, c.nu, c.N, g.Uplan, g.Xplan, g.gU, g.gX, g.gVN, g.gA, g.gB, g.gx0);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    rc = upload_shared(h, c, nullptr, g.so);
+    if (rc) return rc;
+    g.sh = (const double *)h->shared.p;
+    if (!lqmpc::launch_pgrad(g, h->stream)) return fail(LQMPC_ERR_HIP, "lqmpc_plan_grad_kernel launch failed");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // the element counts of the seven outputs: per instance times Bsz, with reduce as they are
 static void cgrad_counts(int nx, int nu, int N, size_t n[7])
 {
@@ -871,6 +906,18 @@ int lqmpc_cost_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bs
     lqmpc::CGradParams g{nx, nu, N, Bsz, dA, dB, Bsz, 1, dUplan, dXplan, dstatus, nullptr, {}, dgu0, dgVN, reduce ? 1 : 0,
                          {dgQ, dgR, dgP, dglb, dgub, dgxref, dguref}, (long long *)dnskipped, nullptr};
     return cgrad_launch(h, c, g);
+}
+
+int lqmpc_plan_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *dA, const double *dB,
+                              const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                              const double *x_ref, const double *u_ref, const double *dUplan, const double *dXplan,
+                              const int32_t *dstatus, const double *dgUplan, const double *dgXplan, const double *dgVN,
+                              double *dgA, double *dgB, double *dgx0)
+{
+    if (!h || !dA || !dB) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
+    lqmpc::PGradParams g{nx, nu, N, Bsz, dA, dB, Bsz, 1, dUplan, dXplan, dstatus, nullptr, {}, dgUplan, dgXplan, dgVN, dgA, dgB, dgx0};
+    return pgrad_launch(h, &c, c, g);
 }
 
 int64_t lqmpc_cost_grad_blocks(int nx, int nu, int N, int64_t Bsz, int reduce)
@@ -1136,6 +1183,29 @@ int lqmpc_cost_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, c
     rc = s.upload();
     if (!rc) rc = lqmpc_cost_grad_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, x_ref, u_ref, dUp, dXp, dst, dgu, dgV, reduce,
                                             d[0], d[1], d[2], d[3], d[4], d[5], d[6], dns);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_plan_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B,
+                          const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                          const double *x_ref, const double *u_ref, const double *Uplan, const double *Xplan, const int32_t *status,
+                          const double *gUplan, const double *gXplan, const double *gVN, double *gA, double *gB, double *gx0)
+{
+    if (!A || !B) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, nullptr, nullptr, nullptr};
+    int rc = pgrad_check(h, &c, nx, nu, N, Uplan, Xplan, gUplan, gXplan, gVN, gA, gB, gx0);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)Bsz;
+    const double *dA, *dB, *dUp, *dXp, *dgU, *dgX, *dgV;
+    const int32_t *dst;
+    double *dgA, *dgB, *dgx;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(Uplan, b * nu * N, dUp); s.in(Xplan, b * nx * (N + 1), dXp);
+    s.in(status, b, dst); s.in(gUplan, b * nu * N, dgU); s.in(gXplan, b * nx * (N + 1), dgX); s.in(gVN, b, dgV);
+    s.out(gA, b * nx * nx, dgA); s.out(gB, b * nx * nu, dgB); s.out(gx0, b * nx, dgx);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_plan_grad_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, x_ref, u_ref, dUp, dXp, dst, dgU, dgX, dgV, dgA, dgB, dgx);
     return rc ? rc : s.finish();
 }
 
@@ -1660,6 +1730,42 @@ int lqmpc_controller_model_grad(lqmpc_controller *c, const double *Uplan, const 
     s.out(gA, b * nx * nx, dgA); s.out(gB, b * nx * nu, dgB); s.out(gx0, b * nx, dgx);
     rc = s.upload();
     if (!rc) rc = lqmpc_controller_model_grad_dev(c, dUp, dXp, dst, dgu, dgV, dgA, dgB, dgx);
+    return rc ? rc : s.finish();
+}
+
+// read-only on the controller: its copies of A and B (on workgroup records the heads of the records) and its current references
+int lqmpc_controller_plan_grad_dev(lqmpc_controller *c, const double *dUplan, const double *dXplan, const int32_t *dstatus,
+                                   const double *dgUplan, const double *dgXplan, const double *dgVN, double *dgA, double *dgB, double *dgx0)
+{
+    if (!c) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    lqmpc::PGradParams g{c->nx, c->nu, c->N, c->Bsz, (const double *)c->A, (const double *)c->B, c->Bsz, 1, dUplan, dXplan, dstatus,
+                         nullptr, {}, dgUplan, dgXplan, dgVN, dgA, dgB, dgx0};
+    if (!c->A) {
+        const lqmpc::WgCtlRec L = lqmpc::wg_ctl_rec_layout(c->nx, c->nu, c->N);
+        g.A = (const double *)c->rec + L.oA; g.B = (const double *)c->rec + L.oB;
+        g.sE = 1; g.sI = L.stride;
+    }
+    return pgrad_launch(c->h, nullptr, ctl_call(c), g);
+}
+
+int lqmpc_controller_plan_grad(lqmpc_controller *c, const double *Uplan, const double *Xplan, const int32_t *status,
+                               const double *gUplan, const double *gXplan, const double *gVN, double *gA, double *gB, double *gx0)
+{
+    if (!c) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    int rc = pgrad_check(c, nullptr, c->nx, c->nu, c->N, Uplan, Xplan, gUplan, gXplan, gVN, gA, gB, gx0);
+    if (rc) return rc;
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)c->Bsz, nx = (size_t)c->nx, nu = (size_t)c->nu, N = (size_t)c->N;
+    const double *dUp, *dXp, *dgU, *dgX, *dgV;
+    const int32_t *dst;
+    double *dgA, *dgB, *dgx;
+    s.in(Uplan, b * nu * N, dUp); s.in(Xplan, b * nx * (N + 1), dXp); s.in(status, b, dst);
+    s.in(gUplan, b * nu * N, dgU); s.in(gXplan, b * nx * (N + 1), dgX); s.in(gVN, b, dgV);
+    s.out(gA, b * nx * nx, dgA); s.out(gB, b * nx * nu, dgB); s.out(gx0, b * nx, dgx);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_controller_plan_grad_dev(c, dUp, dXp, dst, dgU, dgX, dgV, dgA, dgB, dgx);
     return rc ? rc : s.finish();
 }
 

@@ -118,4 +118,23 @@ long long cgrad_blocks(int nx, int nu, int N, long long Bsz, int reduce);   // t
 size_t cgrad_part_bytes(int nx, int nu, int N, long long Bsz);
 bool launch_cgrad(const CGradParams &p, hipStream_t stream);
 
+// lqmpc_pgrad.hip: the post-pass of lqmpc_plan_grad_batch / lqmpc_controller_plan_grad -- from the same plan and the cotangents of
+// every u_i, every x_i and V_N, the gradient with respect to A, B and x_0 of every instance on the plan's face.  One kernel for every
+// shape within the build limits; pgrad_fits says whether its LDS image does (launch_pgrad refuses, and launches nothing, where not).
+struct PGradParams {
+    int nx, nu, N;
+    long long Bsz;
+    const double *A, *B;                  // as SensParams: element e of instance b at A[e * sE + b * sI]
+    long long sE, sI;
+    const double *Uplan, *Xplan;          // what a plan or sens call wrote, instance-minor
+    const int *status;                    // its status (2 gives NaN in every output of the instance); null: all 0
+    const double *sh;                     // shared block (device): Q, R, P, the box and x_ref at the offsets so
+    SharedOff so;
+    const double *gU, *gX, *gVN;          // d loss / d Uplan (nu, N, Bsz), d loss / d Xplan (nx, N + 1, Bsz), d loss / d V_N (Bsz); null = zero
+    double *gA, *gB, *gx0;                // outputs, instance-minor; any may be null
+};
+size_t pgrad_lds_bytes(int nx, int nu, int N);
+bool pgrad_fits(int nx, int nu, int N);
+bool launch_pgrad(const PGradParams &p, hipStream_t stream);
+
 }  // namespace lqmpc

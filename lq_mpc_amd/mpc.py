@@ -358,6 +358,38 @@ class BatchSolver:
                                                       _ptr(ub), _ptr(x_ref), _ptr(u_ref), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus),
                                                       _ptr(dgu0), _ptr(dgVN), _ptr(dgA), _ptr(dgB), _ptr(dgx0)))
 
+    def plan_grad_batch(self, N, A, B, Q, R, P, lb, ub, U_plan, X_plan, status=None, g_Uplan=None, g_Xplan=None, g_VN=None, x_ref=None,
+                        u_ref=None):
+        """The gradient of a loss on the whole plan with respect to the model and the given state of every instance, on the face the
+        plan reports (lqmpc_plan_grad_batch): U_plan, X_plan and status as a want_plan / want_sens call returned them for the same
+        data; g_Uplan (nu, N, Bsz) = d loss / d U_plan, g_Xplan (nx, N + 1, Bsz) = d loss / d X_plan (its stage 0 acts on the given
+        state) and g_VN (Bsz,) = d loss / d V_N, any may be None (zero), not all.  Returns {"g_A": (nx, nx, Bsz), "g_B": (nx, nu, Bsz),
+        "g_x0": (nx, Bsz)}.  The post-pass alone: no solve."""
+        A, B, nx, nu, Bsz = self._dims(A, B)
+        Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
+        lb, ub = _f64(lb, (nu,)), _f64(ub, (nu,))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        U_plan, X_plan = _f64(U_plan, (nu, N, Bsz)), _f64(X_plan, (nx, N + 1, Bsz))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(Bsz)
+        g_Uplan = None if g_Uplan is None else _f64(g_Uplan, (nu, N, Bsz))
+        g_Xplan = None if g_Xplan is None else _f64(g_Xplan, (nx, N + 1, Bsz))
+        g_VN = None if g_VN is None else _f64(g_VN, (Bsz,))
+        gA = np.empty((nx, nx, Bsz)); gB = np.empty((nx, nu, Bsz)); gx = np.empty((nx, Bsz))
+        _lib.check(self._L.lqmpc_plan_grad_batch(self._h, nx, nu, N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P), _ptr(lb), _ptr(ub),
+                                                 _ptr(x_ref), _ptr(u_ref), _ptr(U_plan), _ptr(X_plan), _ptr(status), _ptr(g_Uplan),
+                                                 _ptr(g_Xplan), _ptr(g_VN), _ptr(gA), _ptr(gB), _ptr(gx)))
+        return {"g_A": gA, "g_B": gB, "g_x0": gx}
+
+    def plan_grad_batch_dev(self, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, dUplan, dXplan, dgA=None, dgB=None, dstatus=None, dgUplan=None,
+                            dgXplan=None, dgVN=None, dgx0=None, x_ref=None, u_ref=None):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_plan_grad_batch_dev).  Any of dgA, dgB,
+        dgx0 may be None, not all."""
+        Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        _lib.check(self._L.lqmpc_plan_grad_batch_dev(self._h, nx, nu, N, Bsz, _ptr(dA), _ptr(dB), _ptr(Q), _ptr(R), _ptr(P), _ptr(lb),
+                                                     _ptr(ub), _ptr(x_ref), _ptr(u_ref), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus),
+                                                     _ptr(dgUplan), _ptr(dgXplan), _ptr(dgVN), _ptr(dgA), _ptr(dgB), _ptr(dgx0)))
+
     def cost_grad_batch(self, N, A, B, Q, R, P, lb, ub, U_plan, X_plan, status=None, g_u0=None, g_VN=None, x_ref=None, u_ref=None,
                         reduce=False):
         """The gradient of a loss on (u_0, V_N) with respect to the data the batch shares -- the weights, the references and the box
@@ -543,6 +575,26 @@ class BatchController:
         """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_controller_model_grad_dev)."""
         _lib.check(self._L.lqmpc_controller_model_grad_dev(self._live(), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus), _ptr(dgu0), _ptr(dgVN),
                                                            _ptr(dgA), _ptr(dgB), _ptr(dgx0)))
+
+    def plan_grad(self, U_plan, X_plan, status=None, g_Uplan=None, g_Xplan=None, g_VN=None):
+        """BatchSolver.plan_grad_batch on the controller's own models and current references, for a plan one of its steps returned
+        (lqmpc_controller_plan_grad).  Read-only on the controller."""
+        nx, nu, N, Bsz = self.nx, self.nu, self.N, self.Bsz
+        U_plan, X_plan = _f64(U_plan, (nu, N, Bsz)), _f64(X_plan, (nx, N + 1, Bsz))
+        status = None if status is None else np.ascontiguousarray(status, dtype=np.int32).reshape(Bsz)
+        g_Uplan = None if g_Uplan is None else _f64(g_Uplan, (nu, N, Bsz))
+        g_Xplan = None if g_Xplan is None else _f64(g_Xplan, (nx, N + 1, Bsz))
+        g_VN = None if g_VN is None else _f64(g_VN, (Bsz,))
+        gA = np.empty((nx, nx, Bsz)); gB = np.empty((nx, nu, Bsz)); gx = np.empty((nx, Bsz))
+        _lib.check(self._L.lqmpc_controller_plan_grad(self._live(), _ptr(U_plan), _ptr(X_plan), _ptr(status), _ptr(g_Uplan), _ptr(g_Xplan),
+                                                      _ptr(g_VN), _ptr(gA), _ptr(gB), _ptr(gx)))
+        return {"g_A": gA, "g_B": gB, "g_x0": gx}
+
+    def plan_grad_dev(self, dUplan, dXplan, dgA=None, dgB=None, dstatus=None, dgUplan=None, dgXplan=None, dgVN=None, dgx0=None):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_controller_plan_grad_dev).  Any of dgA,
+        dgB, dgx0 may be None, not all."""
+        _lib.check(self._L.lqmpc_controller_plan_grad_dev(self._live(), _ptr(dUplan), _ptr(dXplan), _ptr(dstatus), _ptr(dgUplan),
+                                                          _ptr(dgXplan), _ptr(dgVN), _ptr(dgA), _ptr(dgB), _ptr(dgx0)))
 
     def cost_grad(self, U_plan, X_plan, status=None, g_u0=None, g_VN=None, reduce=False):
         """BatchSolver.cost_grad_batch on the controller's own models, weights, box and current references, for a plan one of its

@@ -7,6 +7,8 @@
     loss(u0, VN).backward()                              # x.grad, and A.grad, B.grad through the model of every instance
     u0, VN = layer(x, x_ref=xr, u_ref=ur)                # xr (nx, N), ur (nu, N) fp64 CPU tensors, possibly requires_grad: the new references
     loss(u0, VN).backward()                              # x.grad, and xr.grad, ur.grad summed over the batch (with A, B: theirs too)
+    Uplan, Xplan, VN = layer.plan(x, A, B)               # the whole plan (nu, N, Bsz), its states (nx, N + 1, Bsz) and VN; A, B optional
+    loss(Uplan, Xplan, VN).backward()                    # x.grad, A.grad, B.grad for a loss on every u_i, every x_i and V_N
 
 Forward is one lqmpc_controller_step_sens_dev on the tensors' own pointers: the QP of every instance, then the post-pass that returns
 K_0 = d u_0 / d x and dV_N / d x on the face the plan ends on.  Backward is  grad_x = K_0' grad_u0 + dV_dx grad_VN, a torch einsum.
@@ -19,6 +21,9 @@ host data, as everywhere in the library, so they are CPU tensors; one left out i
 lqmpc_controller_cost_grad_dev with reduce (csrc/lqmpc_cgrad.hip), which sums the gradient with respect to the references over the
 batch on the GPU, and copies the two small results to the host: that copy is the one wait for the host in the layer, and it happens
 on this path only.  Backward raises if a set_reference or a set_model came between the forward and its backward.
+layer.plan is one lqmpc_controller_step_plan_dev forward (behind set_model where A and B are given) and one
+lqmpc_controller_plan_grad_dev backward (csrc/lqmpc_pgrad.hip), which returns grad_x and, where asked for, grad_A and grad_B: no einsum,
+no K_plan, no wait for the host; backward raises behind an intervening set_model or set_reference in the same way.
 The solver handle is created on torch's current stream (lqmpc_create_on_stream), so everything is ordered with the surrounding torch
 work on that stream and, but for that copy, nothing waits for the host, in forward or in backward.  Use the layer under the stream it
 was made under.
@@ -163,6 +168,49 @@ class _MPCStepRefs(torch.autograd.Function):
         return grad_x, grad_A, grad_B, grad_xr, grad_ur, None
 
 
+class _MPCPlan(torch.autograd.Function):
+    """the step returning its whole plan (and, where given, under new models A, B): differentiable in x, A and B"""
+
+    @staticmethod
+    def forward(ctx, x, A, B, ctl):
+        nx, nu, N, Bsz = ctl.nx, ctl.nu, ctl.N, ctl.Bsz
+        if x.dtype != torch.float64 or not x.is_cuda or tuple(x.shape) != (nx, Bsz):
+            raise ValueError(f"x must be a float64 device tensor of shape ({nx}, {Bsz})")
+        if A is not None:
+            for M, shape in ((A, (nx, nx, Bsz)), (B, (nx, nu, Bsz))):
+                if M.dtype != torch.float64 or not M.is_cuda or tuple(M.shape) != shape:
+                    raise ValueError(f"A and B must be float64 device tensors of shapes ({nx}, {nx}, {Bsz}) and ({nx}, {nu}, {Bsz})")
+            ctl.set_model(A.detach().contiguous(), B.detach().contiguous())
+        x = x.detach().contiguous()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=x.device)
+        u0, VN, Up, Xp = new(nu, Bsz), new(Bsz), new(nu, N, Bsz), new(nx, N + 1, Bsz)
+        st = torch.empty(Bsz, dtype=torch.int32, device=x.device)
+        ctl.step_plan_dev(x, u0, Up, dXplan=Xp, dVN=VN, dstatus=st)
+        ctx.save_for_backward(Up, Xp, st)
+        ctx.ctl, ctx.model_version, ctx.reference_version = ctl, ctl.model_version, ctl.reference_version
+        return Up, Xp, VN
+
+    @staticmethod
+    def backward(ctx, grad_U, grad_X, grad_VN):
+        Up, Xp, st = ctx.saved_tensors
+        ctl = ctx.ctl
+        if ctl.model_version != ctx.model_version:
+            raise RuntimeError("MPCLayer: the controller's models were replaced (set_model) between this forward and its backward; "
+                               "the gradient would be that of another model")
+        if ctl.reference_version != ctx.reference_version:
+            raise RuntimeError("MPCLayer: the controller's references were replaced (set_reference) between this forward and its "
+                               "backward; the gradient would be that of other references")
+        if grad_U is None and grad_X is None and grad_VN is None:
+            return None, None, None, None
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=Xp.device)
+        grad_x = new(ctl.nx, ctl.Bsz)
+        grad_A = new(ctl.nx, ctl.nx, ctl.Bsz) if ctx.needs_input_grad[1] else None
+        grad_B = new(ctl.nx, ctl.nu, ctl.Bsz) if ctx.needs_input_grad[2] else None
+        cot = [None if g is None else g.contiguous() for g in (grad_U, grad_X, grad_VN)]
+        ctl.plan_grad_dev(Up, Xp, grad_A, grad_B, dstatus=st, dgUplan=cot[0], dgXplan=cot[1], dgVN=cot[2], dgx0=grad_x)
+        return grad_x, grad_A, grad_B, None
+
+
 class MPCLayer(torch.nn.Module):
     """u0, VN = MPCLayer(N, A, B, Q, R, P, lb, ub)(x) around a BatchController; options are the solver's (BatchSolver.set_options).
     layer(x, A, B) steps under the models A, B (they become the controller's) and is differentiable in them as well;
@@ -185,6 +233,14 @@ class MPCLayer(torch.nn.Module):
         if A is None:
             return _MPCStep.apply(x, self.controller)
         return _MPCStepModel.apply(x, A, B, self.controller)
+
+    def plan(self, x, A=None, B=None):
+        """Uplan (nu, N, Bsz), Xplan (nx, N + 1, Bsz), VN (Bsz,) of one step at x, under the models A, B where given (they become the
+        controller's, as in forward).  Differentiable in x, A and B for a loss on all three: backward is one
+        lqmpc_controller_plan_grad_dev on the face the plan ends on."""
+        if (A is None) != (B is None):
+            raise ValueError("give both A and B, or neither")
+        return _MPCPlan.apply(x, A, B, self.controller)
 
     def close(self):
         self.controller.close()
