@@ -406,6 +406,78 @@ int lqmpc_rollout_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
                             const double *x_ref, const double *u_ref,
                             double *dJT, double *dX, double *dU, int32_t *dstatus, int32_t *diters);
 
+/* ---- the same closed loop, leaving a tape: the whole plan of every step ----
+ * Arguments as lqmpc_rollout_batch[_dev], plus
+ *     Utape[t*(nu*N*Bsz) + (k*N + i)*Bsz + b] = u_i[k] of the plan solved at step t   (required)
+ *     status_tape[t*Bsz + b]                  = the status of that solve              (may be NULL)
+ * so slice t of Utape is a valid Uplan for every post-pass call above.  X, U, status, iters may be NULL.
+ * THIS IS NOT THE FAST ROLLOUT.  Per step, on the handle's stream: the path of lqmpc_solve_plan_batch_dev on x_t, its plan written
+ * straight into slice t, then one launch of lqmpc_plant_step_kernel (one lane per instance): x_{t+1} = A_true x_t + B_true u_0, the
+ * cost in the order of the reference (x_0'Q x_0 first, then x_{t+1}'Q x_{t+1} + u_0'R u_0 per step), row t + 1 of X, row t of U, and
+ * x_{t+1} into one of two (nx, Bsz) buffers of the handle for the next solve.  That is 2 T launches (more where a solve hands
+ * instances back) against the one or two of lqmpc_rollout_batch_dev: the price of the tape (DESIGN.md section 4.14 has the figures).
+ * Contract: U[:, t] is bit for bit Utape[t][:, 0]; slice t obeys the plan contract of lqmpc_solve_plan_batch, its forms of a bound
+ * included; JT, X and U agree with lqmpc_rollout_batch[_dev] within the accuracy contract stated at lqmpc_solve_batch, not bit for
+ * bit (the rollout kernels warm-start and sum in another order); status[b] is the largest status over the steps, iters[b] the sum.
+ * _dev returns at once.  NULL handle, model, x0, JT, plant or Utape, T outside [1, 100000]: LQMPC_ERR_BAD_ARG before anything is
+ * enqueued. */
+int lqmpc_rollout_tape_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T,
+                             const double *A, const double *B,
+                             const double *Q, const double *R, const double *P,
+                             const double *lb, const double *ub, const double *x0,
+                             const double *A_true, const double *B_true, int true_per_instance,
+                             const double *x_ref, const double *u_ref,
+                             double *JT, double *X, double *U, int32_t *status, int32_t *iters,
+                             double *Utape, int32_t *status_tape);
+int lqmpc_rollout_tape_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T,
+                                 const double *dA, const double *dB,
+                                 const double *Q, const double *R, const double *P,
+                                 const double *lb, const double *ub, const double *dx0,
+                                 const double *A_true, const double *B_true, int true_per_instance,
+                                 const double *x_ref, const double *u_ref,
+                                 double *dJT, double *dX, double *dU, int32_t *dstatus, int32_t *diters,
+                                 double *dUtape, int32_t *dstatus_tape);
+
+/* ---- the gradient of a loss on the closed loop -- J_T, every x_t and every u_t -- with respect to the model, the plant and x_0 ----
+ * Given what lqmpc_rollout_tape_batch wrote (X, Utape, status_tape; status_tape may be NULL = all 0) and the cotangents
+ *     gJT[b] = d loss / d J_T     gX[(a*(T+1) + t)*Bsz + b] = d loss / d x_t[a]     gU[(k*T + t)*Bsz + b] = d loss / d u_t[k]
+ * (any may be NULL = zero, not all), instance-minor:
+ *     gA[(a*nx + c)*Bsz + b], gB[(a*nu + k)*Bsz + b]            = d loss / d the MODEL of instance b (it drives every QP)
+ *     gA_true[(a*nx + c)*Bsz + b], gB_true[(a*nu + k)*Bsz + b]  = d loss / d the PLANT of instance b: always per instance, a caller
+ *                                                                 with a shared plant (true_per_instance == 0) sums them
+ *     gx0[a*Bsz + b]                                            = d loss / d x_0[a]
+ * Any output may be NULL, not all.  The call is one launch of lqmpc_rollout_grad_kernel on the handle's stream and runs no solve; the
+ * data must be those of the call that wrote the tape.  Per instance, with gam = gJT, the tape is walked backwards with the plant's costate:
+ *     l_T = gX_T + 2 gam Q x_T;   t = T-1 .. 0:   w_t = gU_t + 2 gam R u_t + B_true'l_{t+1}
+ *         (gA_t, gB_t, gx_t) = the gradient of lqmpc_model_grad_batch at step t for gu0 = w_t, gVN = 0, on the face slice t reports
+ *         gA += gA_t, gB += gB_t, gA_true += l_{t+1} x_t', gB_true += l_{t+1} u_t',   l_t = gX_t + 2 gam Q x_t + A_true'l_{t+1} + gx_t
+ *     gx0 = l_0
+ * The face of a step is the one its slice reports, by the rule of lqmpc_solve_sens_batch (bit for bit lb_k, ub_k, c_k - h_k or
+ * c_k + h_k; no tolerance); the states of a plan are re-rolled on the model from x_t and the slice.  At the border of two critical
+ * regions the gradient is one-sided.  A step whose stage-0 inputs all sit on bounds adds exactly nothing from its QP; an instance
+ * whose cotangents are all 0.0 gets exact 0.0 everywhere; an instance with status 2 at any step gets NaN in every output.  NULL
+ * handle, model, plant, X or Utape, all cotangents NULL, all outputs NULL, T outside [1, 100000]: LQMPC_ERR_BAD_ARG; a shape whose LDS
+ * image would not fit 160 KiB: LQMPC_ERR_UNSUPPORTED (the image is larger than that of lqmpc_plan_grad_kernel: the shapes DESIGN.md
+ * section 4.14 lists); both before anything is enqueued. */
+int lqmpc_rollout_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T,
+                             const double *A, const double *B,
+                             const double *Q, const double *R, const double *P,
+                             const double *lb, const double *ub,
+                             const double *A_true, const double *B_true, int true_per_instance,
+                             const double *x_ref, const double *u_ref,
+                             const double *X, const double *Utape, const int32_t *status_tape,
+                             const double *gJT, const double *gX, const double *gU,
+                             double *gA, double *gB, double *gx0, double *gA_true, double *gB_true);
+int lqmpc_rollout_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T,
+                                 const double *dA, const double *dB,
+                                 const double *Q, const double *R, const double *P,
+                                 const double *lb, const double *ub,
+                                 const double *A_true, const double *B_true, int true_per_instance,
+                                 const double *x_ref, const double *u_ref,
+                                 const double *dX, const double *dUtape, const int32_t *dstatus_tape,
+                                 const double *dgJT, const double *dgX, const double *dgU,
+                                 double *dgA, double *dgB, double *dgx0, double *dgA_true, double *dgB_true);
+
 /* ---- M_V = max_k V_N(x0s[:,k]) per instance (utils_class.py:816-824, 899-907) ---- */
 int lqmpc_max_vn_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int K,
                        const double *A, const double *B,

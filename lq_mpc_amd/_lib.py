@@ -41,6 +41,7 @@ EXPORTS = [
     "lqmpc_cost_grad_batch", "lqmpc_cost_grad_batch_dev", "lqmpc_controller_cost_grad", "lqmpc_controller_cost_grad_dev",
     "lqmpc_cost_grad_blocks",
     "lqmpc_plan_grad_batch", "lqmpc_plan_grad_batch_dev", "lqmpc_controller_plan_grad", "lqmpc_controller_plan_grad_dev",
+    "lqmpc_rollout_tape_batch", "lqmpc_rollout_tape_batch_dev", "lqmpc_rollout_grad_batch", "lqmpc_rollout_grad_batch_dev",
 ]
 
 
@@ -113,6 +114,11 @@ def lib():
     roll_args = dims + [ctypes.c_int] + [P] * 10 + [ctypes.c_int] + [P] * 7
     L.lqmpc_rollout_batch.argtypes = roll_args
     L.lqmpc_rollout_batch_dev.argtypes = roll_args
+    L.lqmpc_rollout_tape_batch.argtypes = roll_args + [P] * 2
+    L.lqmpc_rollout_tape_batch_dev.argtypes = roll_args + [P] * 2
+    rgrad_args = dims + [ctypes.c_int] + [P] * 9 + [ctypes.c_int] + [P] * 13
+    L.lqmpc_rollout_grad_batch.argtypes = rgrad_args
+    L.lqmpc_rollout_grad_batch_dev.argtypes = rgrad_args
     mv_args = dims + [ctypes.c_int] + [P] * 13
     L.lqmpc_max_vn_batch.argtypes = mv_args
     L.lqmpc_max_vn_batch_dev.argtypes = mv_args

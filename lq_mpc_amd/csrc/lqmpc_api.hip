@@ -55,6 +55,7 @@ struct lqmpc_handle {
     DevBuf st2, it2;                 // lqmpc_sweep_batch_dev without a fused kernel: status / iters of the max-V_N pass
     DevBuf sens_u, sens_x, sens_st;  // lqmpc_*_sens*: the plan, its states and the status where the caller passed NULL
     DevBuf cgrad_part;               // lqmpc_*_cost_grad* with reduce: the partial sums of every wavefront
+    DevBuf tape;                     // lqmpc_rollout_tape_batch_dev: x_t of two steps in turn, u_0, V_N, status and iters of one solve
     DevBuf arena;                    // host-flavour staging (Stager): every array of the call in one block
     HostBuf arena_pin;               // ... its pinned image, for the small calls that go up and come back in one copy each
     HostBuf shared_pin[2];           // source of the shared block's upload
@@ -186,7 +187,7 @@ int lqmpc_destroy(lqmpc_handle *h)
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (DevBuf *b : {&h->shared, &h->ws, &h->key, &h->perm, &h->rec, &h->fail, &h->st2, &h->it2, &h->sens_u, &h->sens_x, &h->sens_st, &h->cgrad_part, &h->arena}) if (b->p) (void)hipFree(b->p);
+    for (DevBuf *b : {&h->shared, &h->ws, &h->key, &h->perm, &h->rec, &h->fail, &h->st2, &h->it2, &h->sens_u, &h->sens_x, &h->sens_st, &h->cgrad_part, &h->tape, &h->arena}) if (b->p) (void)hipFree(b->p);
     for (HostBuf *b : {&h->arena_pin, &h->shared_pin[0], &h->shared_pin[1]}) {
         if (b->p) (void)hipHostFree(b->p);
         if (b->ev) (void)hipEventDestroy(b->ev);
@@ -939,6 +940,96 @@ int lqmpc_rollout_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
     return rollout_dev(h, h->opt, c, dA, dB, dx0, A_true, B_true, dJT, dX, dU, dstatus, diters);
 }
 
+// The closed loop with a tape: per step the path of lqmpc_solve_plan_batch_dev on x_t, its plan written into slice t of the tape, and
+// one launch of lqmpc_plant_step_kernel behind it.  The shared block is that of a solve with the shared plant in its At, Bt slots
+// (a solve kernel never reads them), so it is packed T times, compared T times and uploaded once.
+int lqmpc_rollout_tape_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *dA, const double *dB,
+                                 const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                                 const double *dx0, const double *A_true, const double *B_true, int true_per_instance,
+                                 const double *x_ref, const double *u_ref, double *dJT, double *dX, double *dU,
+                                 int32_t *dstatus, int32_t *diters, double *dUtape, int32_t *dstatus_tape)
+{
+    if (!h || !dA || !dB || !dx0 || !dJT || !A_true || !B_true || !dUtape) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (T < 1 || T > 100000) return fail(LQMPC_ERR_BAD_ARG, "T must be in [1,100000]");
+    const bool per = true_per_instance != 0;
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, per ? nullptr : A_true, per ? nullptr : B_true,
+                 nullptr};
+    int rc = check_call(c);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    // the handle's block: [x of two steps | u_0 | V_N] in doubles, then [status | iters] of one solve
+    const size_t b = (size_t)Bsz, dbl = b * (2 * (size_t)nx + nu + 1);
+    rc = ensure(h, h->tape, dbl * sizeof(double) + 2 * b * sizeof(int32_t));
+    if (rc) return rc;
+    double *xb[2] = {(double *)h->tape.p, (double *)h->tape.p + b * nx};
+    double *u0 = xb[1] + b * nx, *vn = u0 + b * nu;
+    int32_t *st = (int32_t *)(vn + b), *it = st + b;
+    const size_t slice = b * nu * N;
+    for (int t = 0; t < T; ++t) {
+        const double *x = t == 0 ? dx0 : xb[t & 1];
+        int32_t *st_t = dstatus_tape ? dstatus_tape + (size_t)t * b : st;
+        lqmpc::SharedOff so;
+        rc = solve_dev(h, h->opt, c, dA, dB, x, u0, vn, st_t, it, dUtape + (size_t)t * slice, nullptr, &so);
+        if (rc) return rc;
+        const double *sh = (const double *)h->shared.p;
+        lqmpc::PlantStepParams s{nx, nu, N, T, t, Bsz, per ? A_true : sh + so.At, per ? B_true : sh + so.Bt, per ? Bsz : 1, per ? 1 : 0,
+                                 sh, so, x, dUtape + (size_t)t * slice, st_t, it, xb[(t + 1) & 1], dJT, dX, dU, dstatus, diters};
+        lqmpc::launch_plant_step(s, h->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// The gradient of that loop: the checks, the shared block of the tape call (so nothing is copied again) and one launch of
+// lqmpc_rollout_grad_kernel.  No solve: nothing is routed or compiled, and lqmpc_last_kernel is left naming the solve kernel.
+static int rgrad_check(const void *h, const Call &c, int T, const double *A, const double *B, const double *At, const double *Bt,
+                       const double *X, const double *Utape, const double *gJT, const double *gX, const double *gU, const double *gA,
+                       const double *gB, const double *gx0, const double *gAt, const double *gBt)
+{
+    if (!h || !A || !B || !At || !Bt || !X || !Utape) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (!gJT && !gX && !gU) return fail(LQMPC_ERR_BAD_ARG, "gJT, gX and gU are all NULL: there is no cotangent");
+    if (!gA && !gB && !gx0 && !gAt && !gBt) return fail(LQMPC_ERR_BAD_ARG, "every output is NULL");
+    if (T < 1 || T > 100000) return fail(LQMPC_ERR_BAD_ARG, "T must be in [1,100000]");
+    const int rc = check_call(c);
+    if (rc) return rc;
+    if (!lqmpc::rgrad_fits(c.nx, c.nu, c.N)) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "lqmpc_rollout_grad_kernel needs %zu bytes of LDS at (%d,%d,%d): over 160 KiB",
+                 lqmpc::rgrad_lds_bytes(c.nx, c.nu, c.N), c.nx, c.nu, c.N);
+        return fail(LQMPC_ERR_UNSUPPORTED, buf);
+    }
+    return 0;
+}
+
+int lqmpc_rollout_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *dA, const double *dB,
+                                 const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                                 const double *A_true, const double *B_true, int true_per_instance, const double *x_ref,
+                                 const double *u_ref, const double *dX, const double *dUtape, const int32_t *dstatus_tape,
+                                 const double *dgJT, const double *dgX, const double *dgU, double *dgA, double *dgB, double *dgx0,
+                                 double *dgA_true, double *dgB_true)
+{
+    const bool per = true_per_instance != 0;
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, per ? nullptr : A_true, per ? nullptr : B_true,
+                 nullptr};
+    int rc = rgrad_check(h, c, T, dA, dB, A_true, B_true, dX, dUtape, dgJT, dgX, dgU, dgA, dgB, dgx0, dgA_true, dgB_true);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    lqmpc::RGradParams g{};
+    rc = upload_shared(h, c, nullptr, g.so);
+    if (rc) return rc;
+    const double *sh = (const double *)h->shared.p;
+    g.nx = nx; g.nu = nu; g.N = N; g.T = T; g.Bsz = Bsz;
+    g.A = dA; g.B = dB;
+    g.At = per ? A_true : sh + g.so.At; g.Bt = per ? B_true : sh + g.so.Bt;
+    g.sE = per ? Bsz : 1; g.sI = per ? 1 : 0;
+    g.X = dX; g.Utape = dUtape; g.status_tape = dstatus_tape; g.sh = sh;
+    g.gJT = dgJT; g.gX = dgX; g.gU = dgU;
+    g.gA = dgA; g.gB = dgB; g.gx0 = dgx0; g.gAt = dgA_true; g.gBt = dgB_true;
+    if (!lqmpc::launch_rgrad(g, h->stream)) return fail(LQMPC_ERR_HIP, "lqmpc_rollout_grad_kernel launch failed");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int lqmpc_max_vn_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int K, const double *dA, const double *dB,
                            const double *Q, const double *R, const double *P, const double *lb, const double *ub,
                            const double *x0s, const double *x_ref, const double *u_ref, double *dMV, int32_t *dstatus,
@@ -1231,6 +1322,61 @@ int lqmpc_rollout_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int
     rc = s.upload();
     if (!rc) rc = lqmpc_rollout_batch_dev(h, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dx0, dAt, dBt, true_per_instance, x_ref,
                                           u_ref, dJT, dX, dU, dst, dit);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_rollout_tape_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *A, const double *B,
+                             const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                             const double *x0, const double *A_true, const double *B_true, int true_per_instance,
+                             const double *x_ref, const double *u_ref, double *JT, double *X, double *U, int32_t *status,
+                             int32_t *iters, double *Utape, int32_t *status_tape)
+{
+    if (!h || !A || !B || !x0 || !JT || !A_true || !B_true || !Utape) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    int rc = check_dims(nx, nu, N, Bsz);
+    if (rc) return rc;
+    if (T < 1 || T > 100000) return fail(LQMPC_ERR_BAD_ARG, "T must be in [1,100000]");
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)Bsz;
+    const double *dA, *dB, *dx0, *dAt = A_true, *dBt = B_true;
+    double *dJT, *dX, *dU, *dUt;
+    int32_t *dst, *dit, *dstt;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(x0, b * nx, dx0);
+    if (true_per_instance) { s.in(A_true, b * nx * nx, dAt); s.in(B_true, b * nx * nu, dBt); }
+    s.out(JT, b, dJT); s.out(X, b * nx * (T + 1), dX); s.out(U, b * nu * T, dU); s.out(status, b, dst); s.out(iters, b, dit);
+    s.out(Utape, b * nu * N * T, dUt); s.out(status_tape, b * T, dstt);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_rollout_tape_batch_dev(h, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dx0, dAt, dBt, true_per_instance, x_ref,
+                                               u_ref, dJT, dX, dU, dst, dit, dUt, dstt);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_rollout_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *A, const double *B,
+                             const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                             const double *A_true, const double *B_true, int true_per_instance, const double *x_ref,
+                             const double *u_ref, const double *X, const double *Utape, const int32_t *status_tape, const double *gJT,
+                             const double *gX, const double *gU, double *gA, double *gB, double *gx0, double *gA_true, double *gB_true)
+{
+    const bool per = true_per_instance != 0;
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, per ? nullptr : A_true, per ? nullptr : B_true,
+                 nullptr};
+    int rc = rgrad_check(h, c, T, A, B, A_true, B_true, X, Utape, gJT, gX, gU, gA, gB, gx0, gA_true, gB_true);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)Bsz;
+    const double *dA, *dB, *dAt = A_true, *dBt = B_true, *dX, *dUt, *dgJ, *dgX, *dgU;
+    const int32_t *dstt;
+    double *dgA, *dgB, *dgx, *dgAt, *dgBt;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB);
+    if (per) { s.in(A_true, b * nx * nx, dAt); s.in(B_true, b * nx * nu, dBt); }
+    s.in(X, b * nx * (T + 1), dX); s.in(Utape, b * nu * N * T, dUt); s.in(status_tape, b * T, dstt);
+    s.in(gJT, b, dgJ); s.in(gX, b * nx * (T + 1), dgX); s.in(gU, b * nu * T, dgU);
+    s.out(gA, b * nx * nx, dgA); s.out(gB, b * nx * nu, dgB); s.out(gx0, b * nx, dgx);
+    s.out(gA_true, b * nx * nx, dgAt); s.out(gB_true, b * nx * nu, dgBt);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_rollout_grad_batch_dev(h, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dAt, dBt, true_per_instance, x_ref, u_ref, dX,
+                                               dUt, dstt, dgJ, dgX, dgU, dgA, dgB, dgx, dgAt, dgBt);
     return rc ? rc : s.finish();
 }
 

@@ -137,4 +137,40 @@ size_t pgrad_lds_bytes(int nx, int nu, int N);
 bool pgrad_fits(int nx, int nu, int N);
 bool launch_pgrad(const PGradParams &p, hipStream_t stream);
 
+// lqmpc_rgrad.hip: the closed loop with a tape and its gradient (lqmpc_rollout_tape_batch, lqmpc_rollout_grad_batch).
+// The plant step behind the plan call of step t: x_{t+1} = A_true x_t + B_true u_0, the cost, row t + 1 of X, row t of U.
+struct PlantStepParams {
+    int nx, nu, N, T, t;
+    long long Bsz;
+    const double *At, *Bt;                // element e of the plant of instance b at At[e * sE + b * sI]: instance-minor arrays
+    long long sE, sI;                     // (sE = Bsz, sI = 1) or the shared block's single matrices (sE = 1, sI = 0)
+    const double *sh;                     // shared block (device): Q and R at the offsets so
+    SharedOff so;
+    const double *x;                      // x_t (nx, Bsz), instance-minor: x0 at t = 0, then the handle's buffer of the step before
+    const double *Uslice;                 // slice t of the tape: u_0[k] at Uslice[k * N * Bsz + b]
+    const int *st, *it;                   // status and iters of the solve of step t
+    double *xn;                           // x_{t+1} (nx, Bsz): the handle's other buffer
+    double *JT, *X, *U;                   // X, U may be null
+    int *status, *iters;                  // the largest status and the sum of the iterations so far; may be null
+};
+void launch_plant_step(const PlantStepParams &p, hipStream_t stream);
+
+// ... and the gradient of a loss on (J_T, X, U) of that loop with respect to the model, the plant and x_0, from the tape: one launch.
+struct RGradParams {
+    int nx, nu, N, T;
+    long long Bsz;
+    const double *A, *B;                  // the model, instance-minor
+    const double *At, *Bt;                // the plant, as PlantStepParams
+    long long sE, sI;
+    const double *X, *Utape;              // (nx, T + 1, Bsz) and T plans (nu, N, Bsz)
+    const int *status_tape;               // (T, Bsz); 2 at any step gives NaN in every output of the instance; null: all 0
+    const double *sh;                     // shared block (device): Q, R, P, the box and x_ref at the offsets so
+    SharedOff so;
+    const double *gJT, *gX, *gU;          // d loss / d J_T (Bsz), d X (nx, T + 1, Bsz), d U (nu, T, Bsz); null = zero
+    double *gA, *gB, *gx0, *gAt, *gBt;    // outputs, instance-minor; any may be null
+};
+size_t rgrad_lds_bytes(int nx, int nu, int N);
+bool rgrad_fits(int nx, int nu, int N);
+bool launch_rgrad(const RGradParams &p, hipStream_t stream);
+
 }  // namespace lqmpc

@@ -240,6 +240,57 @@ class BatchSolver:
                                                _ptr(status), _ptr(iters)))
         return {"J_T": JT, "X": X, "U": U, "status": status, "iters": iters}
 
+    @staticmethod
+    def _plant(A_true, B_true, nx, nu, Bsz):
+        """the plant of a rollout: single matrices shared by the batch or instance-minor arrays; (A_true, B_true, per_instance)"""
+        A_true, B_true = _f64(A_true), _f64(B_true)
+        if A_true.ndim == 3:
+            return _f64(A_true, (nx, nx, Bsz)), _f64(B_true, (nx, nu, Bsz)), 1
+        return _f64(A_true, (nx, nx)), _f64(B_true, (nx, nu)), 0
+
+    def rollout_tape_batch(self, T, N, A, B, Q, R, P, lb, ub, x0, A_true, B_true, x_ref=None, u_ref=None):
+        """The closed loop of rollout_batch, leaving a tape (lqmpc_rollout_tape_batch): "J_T" (Bsz,), "X" (nx, T + 1, Bsz),
+        "U" (nu, T, Bsz), "U_tape" (T, nu, N, Bsz) -- the whole plan of every step, U_tape[t] a valid U_plan for every post-pass call
+        -- "status" (Bsz,) the largest over the steps, "status_tape" (T, Bsz) and "iters".  Not the fast rollout: one solve and one
+        plant-step launch per step.  What rollout_grad_batch differentiates."""
+        A, B, nx, nu, Bsz = self._dims(A, B)
+        Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
+        lb, ub, x0 = _f64(lb, (nu,)), _f64(ub, (nu,)), _f64(x0, (nx, Bsz))
+        A_true, B_true, per_inst = self._plant(A_true, B_true, nx, nu, Bsz)
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        JT = np.empty(Bsz); X = np.empty((nx, T + 1, Bsz)); U = np.empty((nu, T, Bsz)); Ut = np.empty((T, nu, N, Bsz))
+        status = np.empty(Bsz, dtype=np.int32); iters = np.empty(Bsz, dtype=np.int32); stt = np.empty((T, Bsz), dtype=np.int32)
+        _lib.check(self._L.lqmpc_rollout_tape_batch(self._h, nx, nu, N, Bsz, T, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P),
+                                                    _ptr(lb), _ptr(ub), _ptr(x0), _ptr(A_true), _ptr(B_true), per_inst,
+                                                    _ptr(x_ref), _ptr(u_ref), _ptr(JT), _ptr(X), _ptr(U), _ptr(status), _ptr(iters),
+                                                    _ptr(Ut), _ptr(stt)))
+        return {"J_T": JT, "X": X, "U": U, "U_tape": Ut, "status": status, "status_tape": stt, "iters": iters}
+
+    def rollout_grad_batch(self, T, N, A, B, Q, R, P, lb, ub, A_true, B_true, X, U_tape, status_tape=None, g_JT=None, g_X=None, g_U=None,
+                           x_ref=None, u_ref=None, want=("g_A", "g_B", "g_x0", "g_A_true", "g_B_true")):
+        """The gradient of a loss on the closed loop with respect to the model, the plant and x0 of every instance, from the tape of
+        rollout_tape_batch (lqmpc_rollout_grad_batch): X (nx, T + 1, Bsz), U_tape (T, nu, N, Bsz), status_tape (T, Bsz) or None;
+        g_JT (Bsz,) = d loss / d J_T, g_X (nx, T + 1, Bsz) = d loss / d X, g_U (nu, T, Bsz) = d loss / d U, any may be None (zero),
+        not all.  Returns the keys of `want`: "g_A" (nx, nx, Bsz), "g_B" (nx, nu, Bsz), "g_x0" (nx, Bsz) and, always per instance (sum
+        them for a shared plant), "g_A_true", "g_B_true".  One kernel launch, no solve."""
+        A, B, nx, nu, Bsz = self._dims(A, B)
+        Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
+        lb, ub = _f64(lb, (nu,)), _f64(ub, (nu,))
+        A_true, B_true, per_inst = self._plant(A_true, B_true, nx, nu, Bsz)
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        X, U_tape = _f64(X, (nx, T + 1, Bsz)), _f64(U_tape, (T, nu, N, Bsz))
+        status_tape = None if status_tape is None else np.ascontiguousarray(status_tape, dtype=np.int32).reshape(T, Bsz)
+        g_JT = None if g_JT is None else _f64(g_JT, (Bsz,))
+        g_X = None if g_X is None else _f64(g_X, (nx, T + 1, Bsz))
+        g_U = None if g_U is None else _f64(g_U, (nu, T, Bsz))
+        shapes = {"g_A": (nx, nx, Bsz), "g_B": (nx, nu, Bsz), "g_x0": (nx, Bsz), "g_A_true": (nx, nx, Bsz), "g_B_true": (nx, nu, Bsz)}
+        out = {k: np.empty(shapes[k]) for k in want}
+        _lib.check(self._L.lqmpc_rollout_grad_batch(self._h, nx, nu, N, Bsz, T, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P), _ptr(lb),
+                                                    _ptr(ub), _ptr(A_true), _ptr(B_true), per_inst, _ptr(x_ref), _ptr(u_ref), _ptr(X),
+                                                    _ptr(U_tape), _ptr(status_tape), _ptr(g_JT), _ptr(g_X), _ptr(g_U),
+                                                    *[_ptr(out.get(k)) for k in shapes]))
+        return out
+
     def max_vn_batch(self, N, A, B, Q, R, P, lb, ub, x0s, x_ref=None, u_ref=None):
         A, B, nx, nu, Bsz = self._dims(A, B)
         Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
@@ -439,6 +490,34 @@ class BatchSolver:
                                                    _ptr(lb), _ptr(ub), _ptr(dx0), _ptr(A_true), _ptr(B_true),
                                                    1 if true_per_instance else 0, _ptr(x_ref), _ptr(u_ref),
                                                    _ptr(dJT), _ptr(dX), _ptr(dU), _ptr(dstatus), _ptr(diters)))
+
+    def rollout_tape_batch_dev(self, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dx0, A_true, B_true, dJT, dUtape, dX=None, dU=None,
+                               dstatus=None, diters=None, dstatus_tape=None, true_per_instance=False, x_ref=None, u_ref=None):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_rollout_tape_batch_dev).  dUtape
+        (T, nu, N, Bsz) is required."""
+        Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
+        if not true_per_instance:
+            A_true, B_true = _f64(A_true, (nx, nx)), _f64(B_true, (nx, nu))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        _lib.check(self._L.lqmpc_rollout_tape_batch_dev(self._h, nx, nu, N, Bsz, T, _ptr(dA), _ptr(dB), _ptr(Q), _ptr(R), _ptr(P),
+                                                        _ptr(lb), _ptr(ub), _ptr(dx0), _ptr(A_true), _ptr(B_true),
+                                                        1 if true_per_instance else 0, _ptr(x_ref), _ptr(u_ref), _ptr(dJT), _ptr(dX),
+                                                        _ptr(dU), _ptr(dstatus), _ptr(diters), _ptr(dUtape), _ptr(dstatus_tape)))
+
+    def rollout_grad_batch_dev(self, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, A_true, B_true, dX, dUtape, dstatus_tape=None, dgJT=None,
+                               dgX=None, dgU=None, dgA=None, dgB=None, dgx0=None, dgA_true=None, dgB_true=None, true_per_instance=False,
+                               x_ref=None, u_ref=None):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_rollout_grad_batch_dev).  Any cotangent
+        and any output may be None, not all of either; dgA_true and dgB_true are per instance also where the plant is shared."""
+        Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
+        if not true_per_instance:
+            A_true, B_true = _f64(A_true, (nx, nx)), _f64(B_true, (nx, nu))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        _lib.check(self._L.lqmpc_rollout_grad_batch_dev(self._h, nx, nu, N, Bsz, T, _ptr(dA), _ptr(dB), _ptr(Q), _ptr(R), _ptr(P),
+                                                        _ptr(lb), _ptr(ub), _ptr(A_true), _ptr(B_true), 1 if true_per_instance else 0,
+                                                        _ptr(x_ref), _ptr(u_ref), _ptr(dX), _ptr(dUtape), _ptr(dstatus_tape), _ptr(dgJT),
+                                                        _ptr(dgX), _ptr(dgU), _ptr(dgA), _ptr(dgB), _ptr(dgx0), _ptr(dgA_true),
+                                                        _ptr(dgB_true)))
 
     def max_vn_batch_dev(self, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, x0s, dMV, dstatus=None, diters=None,
                          x_ref=None, u_ref=None):

@@ -9,6 +9,8 @@
     loss(u0, VN).backward()                              # x.grad, and xr.grad, ur.grad summed over the batch (with A, B: theirs too)
     Uplan, Xplan, VN = layer.plan(x, A, B)               # the whole plan (nu, N, Bsz), its states (nx, N + 1, Bsz) and VN; A, B optional
     loss(Uplan, Xplan, VN).backward()                    # x.grad, A.grad, B.grad for a loss on every u_i, every x_i and V_N
+    JT, X, U = layer.rollout(x0, T, A_true, B_true)      # the closed loop of T steps on the plant A_true, B_true; A, B optional
+    loss(JT, X, U).backward()                            # x0.grad, A_true.grad, B_true.grad (with A, B: theirs too) through the whole loop
 
 Forward is one lqmpc_controller_step_sens_dev on the tensors' own pointers: the QP of every instance, then the post-pass that returns
 K_0 = d u_0 / d x and dV_N / d x on the face the plan ends on.  Backward is  grad_x = K_0' grad_u0 + dV_dx grad_VN, a torch einsum.
@@ -211,6 +213,50 @@ class _MPCPlan(torch.autograd.Function):
         return grad_x, grad_A, grad_B, None
 
 
+class _MPCRollout(torch.autograd.Function):
+    """the closed loop of T steps on a plant of its own: differentiable in x0, the model A, B and the plant A_true, B_true"""
+
+    @staticmethod
+    def forward(ctx, x0, A, B, At, Bt, layer, T):
+        ctl = layer.controller
+        nx, nu, N, Bsz = ctl.nx, ctl.nu, ctl.N, ctl.Bsz
+        if x0.dtype != torch.float64 or not x0.is_cuda or tuple(x0.shape) != (nx, Bsz):
+            raise ValueError(f"x0 must be a float64 device tensor of shape ({nx}, {Bsz})")
+        for M, shape in ((A, (nx, nx, Bsz)), (B, (nx, nu, Bsz)), (At, (nx, nx, Bsz)), (Bt, (nx, nu, Bsz))):
+            if M.dtype != torch.float64 or not M.is_cuda or tuple(M.shape) != shape:
+                raise ValueError(f"the model and the plant must be float64 device tensors of shapes ({nx}, {nx}, {Bsz}) and ({nx}, {nu}, {Bsz})")
+        x0, A, B, At, Bt = (M.detach().contiguous() for M in (x0, A, B, At, Bt))
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=x0.device)
+        JT, X, U, Ut = new(Bsz), new(nx, T + 1, Bsz), new(nu, T, Bsz), new(T, nu, N, Bsz)
+        st = torch.empty((T, Bsz), dtype=torch.int32, device=x0.device)
+        layer.solver.rollout_tape_batch_dev(nx, nu, N, Bsz, T, A, B, *layer._shared, x0, At, Bt, JT, Ut, dX=X, dU=U, dstatus_tape=st,
+                                            true_per_instance=True, **layer._refs)
+        ctx.save_for_backward(A, B, At, Bt, X, Ut, st)
+        ctx.layer, ctx.T = layer, T
+        return JT, X, U
+
+    @staticmethod
+    def backward(ctx, grad_J, grad_X, grad_U):
+        A, B, At, Bt, X, Ut, st = ctx.saved_tensors
+        layer, T = ctx.layer, ctx.T
+        if grad_J is None and grad_X is None and grad_U is None:
+            return None, None, None, None, None, None, None
+        ctl = layer.controller
+        nx, nu, N, Bsz = ctl.nx, ctl.nu, ctl.N, ctl.Bsz
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=X.device)
+        need = ctx.needs_input_grad
+        g_x = new(nx, Bsz)
+        g_A = new(nx, nx, Bsz) if need[1] else None
+        g_B = new(nx, nu, Bsz) if need[2] else None
+        g_At = new(nx, nx, Bsz) if need[3] else None
+        g_Bt = new(nx, nu, Bsz) if need[4] else None
+        cot = [None if g is None else g.contiguous() for g in (grad_J, grad_X, grad_U)]
+        layer.solver.rollout_grad_batch_dev(nx, nu, N, Bsz, T, A, B, *layer._shared, At, Bt, X, Ut, dstatus_tape=st, dgJT=cot[0], dgX=cot[1],
+                                            dgU=cot[2], dgA=g_A, dgB=g_B, dgx0=g_x, dgA_true=g_At, dgB_true=g_Bt, true_per_instance=True,
+                                            **layer._refs)
+        return g_x, g_A, g_B, g_At, g_Bt, None, None
+
+
 class MPCLayer(torch.nn.Module):
     """u0, VN = MPCLayer(N, A, B, Q, R, P, lb, ub)(x) around a BatchController; options are the solver's (BatchSolver.set_options).
     layer(x, A, B) steps under the models A, B (they become the controller's) and is differentiable in them as well;
@@ -224,6 +270,31 @@ class MPCLayer(torch.nn.Module):
         if not hasattr(A, "data_ptr"):
             A, B = np.ascontiguousarray(A, dtype=np.float64), np.ascontiguousarray(B, dtype=np.float64)
         self.controller = BatchController(self.solver, N, A, B, Q, R, P, lb, ub, x_ref, u_ref)
+        # what rollout() passes to the batch calls: the data the layer was made with (the model goes to the device on first use)
+        self._model0 = (A, B)
+        self._shared = tuple(np.ascontiguousarray(M, dtype=np.float64) for M in (Q, R, P, lb, ub))
+        self._refs = dict(x_ref=x_ref, u_ref=u_ref)
+
+    def rollout(self, x0, T, A_true, B_true, A=None, B=None):
+        """J_T (Bsz,), X (nx, T + 1, Bsz), U (nu, T, Bsz) of the closed loop of T steps from x0 (nx, Bsz): the model drives every QP
+        -- A, B where given, else those the layer was made with -- and the plant A_true, B_true drives the state: (nx, nx), (nx, nu)
+        shared by the batch or (nx, nx, Bsz), (nx, nu, Bsz).  Differentiable in x0, A, B, A_true and B_true for a loss on all three
+        outputs.  Forward is one lqmpc_rollout_tape_batch_dev (T plan calls with a plant step behind each: not the fast rollout),
+        backward one lqmpc_rollout_grad_batch_dev (csrc/lqmpc_rgrad.hip) on the tape it left; a shared plant is expanded over the
+        batch in torch, so its gradient is summed by autograd.  The weights, the box and the references are those the layer was made
+        with.  Nothing waits for the host."""
+        if (A is None) != (B is None):
+            raise ValueError("give both A and B, or neither")
+        ctl = self.controller
+        if A is None:
+            if not hasattr(self._model0[0], "data_ptr"):
+                self._model0 = tuple(torch.from_numpy(M).to(x0.device) for M in self._model0)
+            A, B = self._model0
+        plant = []
+        for M in (A_true, B_true):
+            M = M.to(x0.device)
+            plant.append(M.unsqueeze(-1).expand(*M.shape, ctl.Bsz) if M.dim() == 2 else M)
+        return _MPCRollout.apply(x0, A, B, plant[0], plant[1], self, int(T))
 
     def forward(self, x, A=None, B=None, *, x_ref=None, u_ref=None):
         if (A is None) != (B is None):
