@@ -478,6 +478,56 @@ int lqmpc_rollout_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t
                                  const double *dgJT, const double *dgX, const double *dgU,
                                  double *dgA, double *dgB, double *dgx0, double *dgA_true, double *dgB_true);
 
+/* ---- the gradient of the same loss on the closed loop with respect to the data the batch shares: Q, R, P, lb, ub, x_ref, u_ref ----
+ * Inputs as lqmpc_rollout_grad_batch[_dev]: what lqmpc_rollout_tape_batch wrote (X, Utape, status_tape; status_tape may be NULL = all
+ * 0) and the cotangents gJT, gX, gU (any may be NULL = zero, not all).  Outputs and `reduce` as lqmpc_cost_grad_batch[_dev]:
+ *     reduce == 0, per instance, instance-minor:  gQ[(a*nx + c)*Bsz + b], gR[(k*nu + l)*Bsz + b], gP[(a*nx + c)*Bsz + b],
+ *         glb[k*Bsz + b], gub[k*Bsz + b], gxref[(a*N + i)*Bsz + b], guref[(k*N + i)*Bsz + b]
+ *     reduce != 0, the sum over the batch, every output in the shape of its parameter (row-major); *nskipped takes the number of
+ *         instances with status 2 at any step, which add 0.0.  The sum is formed on chip in a fixed order without atomics: the same
+ *         data give the same bits.
+ * Any output may be NULL, not all.  The call is one launch of lqmpc_rollout_cost_grad_kernel on the handle's stream (with reduce, a
+ * second small launch that adds one vector of partial sums per wavefront, kept in a block the handle owns) and runs no solve; the
+ * data must be those of the call that wrote the tape.  Per instance, with gam = gJT, the tape is walked backwards with the plant's costate:
+ *     l_T = gX_T + 2 gam Q x_T;   t = T-1 .. 0:   w_t = gU_t + 2 gam R u_t + B_true'l_{t+1}
+ *         (gQ_t, gR_t, gP_t, glb_t, gub_t, gxref_t, guref_t) = the gradient of lqmpc_cost_grad_batch at step t for gu0 = w_t, gVN = 0,
+ *                                                              on the face slice t reports, plan states re-rolled on the model from x_t
+ *         gx_t = the gx0 of lqmpc_model_grad_batch for the same cotangents (the same adjoint plan)
+ *         every output += its step-t term,   l_t = gX_t + 2 gam Q x_t + A_true'l_{t+1} + gx_t
+ *     the direct part, because the one Q and R of the call also weigh J_T:  gQ += gam sum_{t=0}^{T} x_t x_t',  gR += gam sum_{t=0}^{T-1} u_t u_t'
+ * With gVN = 0 the step-t terms are (xt, ut the adjoint plan, lt its costate, e_i = x_i - xref_{i-1}, d_i = u_i - uref_i):
+ *     gQ_t = -sum_{i=1}^{N-1} (xt_i e_i' + e_i xt_i'),  gP_t the same term at i = N,   gR_t = -sum_i (ut_i d_i' + d_i ut_i')
+ *     gxref_t[:, i-1] = 2 Q xt_i (P at i = N),   guref_t[:, i] = 2 R ut_i
+ *     gub_t[k] = sum over the entries (i, k) on the upper bound of -rt_i[k] + (i == 0 ? w_t[k] : 0),  rt_i = 2 R ut_i + B'lt_{i+1};  glb_t likewise
+ * gQ, gR and gP take the entries of the matrix as independent, as lqmpc_cost_grad_batch does: a caller who parametrises a symmetric
+ * matrix contracts them with its own d Q.  The face rule is that of lqmpc_solve_sens_batch, bit for bit, no tolerance.  A step whose
+ * stage-0 inputs all sit on bounds adds w_t[k] to glb[k] or gub[k] and exactly nothing else; cotangents that are all 0.0 give exact
+ * 0.0 everywhere; per instance, an instance with status 2 at any step gets NaN in every output.
+ * THE CONTROLLER'S WEIGHTS ONLY: a caller who wants the derivative in the weights the controller plans with, under fixed evaluation
+ * weights, passes gJT = NULL and puts the evaluation cost into gX and gU (gX_t = 2 Q_eval x_t, gU_t = 2 R_eval u_t); there is no flag.
+ * NULL handle, model, plant, X or Utape, all cotangents NULL, all outputs NULL, T outside [1, 100000]: LQMPC_ERR_BAD_ARG; a shape whose
+ * LDS image would not fit 160 KiB: LQMPC_ERR_UNSUPPORTED (the shapes DESIGN.md section 4.15 lists); both before anything is enqueued. */
+int lqmpc_rollout_cost_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T,
+                                  const double *A, const double *B,
+                                  const double *Q, const double *R, const double *P,
+                                  const double *lb, const double *ub,
+                                  const double *A_true, const double *B_true, int true_per_instance,
+                                  const double *x_ref, const double *u_ref,
+                                  const double *X, const double *Utape, const int32_t *status_tape,
+                                  const double *gJT, const double *gX, const double *gU, int reduce,
+                                  double *gQ, double *gR, double *gP, double *glb, double *gub, double *gxref, double *guref,
+                                  int64_t *nskipped);
+int lqmpc_rollout_cost_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T,
+                                      const double *dA, const double *dB,
+                                      const double *Q, const double *R, const double *P,
+                                      const double *lb, const double *ub,
+                                      const double *A_true, const double *B_true, int true_per_instance,
+                                      const double *x_ref, const double *u_ref,
+                                      const double *dX, const double *dUtape, const int32_t *dstatus_tape,
+                                      const double *dgJT, const double *dgX, const double *dgU, int reduce,
+                                      double *dgQ, double *dgR, double *dgP, double *dglb, double *dgub, double *dgxref,
+                                      double *dguref, int64_t *dnskipped);
+
 /* ---- M_V = max_k V_N(x0s[:,k]) per instance (utils_class.py:816-824, 899-907) ---- */
 int lqmpc_max_vn_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int K,
                        const double *A, const double *B,

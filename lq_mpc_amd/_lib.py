@@ -42,6 +42,7 @@ EXPORTS = [
     "lqmpc_cost_grad_blocks",
     "lqmpc_plan_grad_batch", "lqmpc_plan_grad_batch_dev", "lqmpc_controller_plan_grad", "lqmpc_controller_plan_grad_dev",
     "lqmpc_rollout_tape_batch", "lqmpc_rollout_tape_batch_dev", "lqmpc_rollout_grad_batch", "lqmpc_rollout_grad_batch_dev",
+    "lqmpc_rollout_cost_grad_batch", "lqmpc_rollout_cost_grad_batch_dev",
 ]
 
 
@@ -119,6 +120,9 @@ def lib():
     rgrad_args = dims + [ctypes.c_int] + [P] * 9 + [ctypes.c_int] + [P] * 13
     L.lqmpc_rollout_grad_batch.argtypes = rgrad_args
     L.lqmpc_rollout_grad_batch_dev.argtypes = rgrad_args
+    rcgrad_args = dims + [ctypes.c_int] + [P] * 9 + [ctypes.c_int] + [P] * 8 + [ctypes.c_int] + [P] * 8
+    L.lqmpc_rollout_cost_grad_batch.argtypes = rcgrad_args
+    L.lqmpc_rollout_cost_grad_batch_dev.argtypes = rcgrad_args
     mv_args = dims + [ctypes.c_int] + [P] * 13
     L.lqmpc_max_vn_batch.argtypes = mv_args
     L.lqmpc_max_vn_batch_dev.argtypes = mv_args

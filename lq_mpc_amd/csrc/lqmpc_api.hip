@@ -55,6 +55,7 @@ struct lqmpc_handle {
     DevBuf st2, it2;                 // lqmpc_sweep_batch_dev without a fused kernel: status / iters of the max-V_N pass
     DevBuf sens_u, sens_x, sens_st;  // lqmpc_*_sens*: the plan, its states and the status where the caller passed NULL
     DevBuf cgrad_part;               // lqmpc_*_cost_grad* with reduce: the partial sums of every wavefront
+    DevBuf rcgrad_part;              // lqmpc_rollout_cost_grad_batch* with reduce: the partial sums of every wavefront
     DevBuf tape;                     // lqmpc_rollout_tape_batch_dev: x_t of two steps in turn, u_0, V_N, status and iters of one solve
     DevBuf arena;                    // host-flavour staging (Stager): every array of the call in one block
     HostBuf arena_pin;               // ... its pinned image, for the small calls that go up and come back in one copy each
@@ -187,7 +188,7 @@ int lqmpc_destroy(lqmpc_handle *h)
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    for (DevBuf *b : {&h->shared, &h->ws, &h->key, &h->perm, &h->rec, &h->fail, &h->st2, &h->it2, &h->sens_u, &h->sens_x, &h->sens_st, &h->cgrad_part, &h->tape, &h->arena}) if (b->p) (void)hipFree(b->p);
+    for (DevBuf *b : {&h->shared, &h->ws, &h->key, &h->perm, &h->rec, &h->fail, &h->st2, &h->it2, &h->sens_u, &h->sens_x, &h->sens_st, &h->cgrad_part, &h->rcgrad_part, &h->tape, &h->arena}) if (b->p) (void)hipFree(b->p);
     for (HostBuf *b : {&h->arena_pin, &h->shared_pin[0], &h->shared_pin[1]}) {
         if (b->p) (void)hipHostFree(b->p);
         if (b->ev) (void)hipEventDestroy(b->ev);
@@ -1030,6 +1031,66 @@ int lqmpc_rollout_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t
     return 0;
 }
 
+// The gradient of that loop in the data the batch shares: the checks, the shared block of the tape call and one launch of
+// lqmpc_rollout_cost_grad_kernel -- with `reduce` followed by the kernel that adds the wavefronts' partial sums, which lie in a block
+// of the handle's own.  No solve: nothing is routed or compiled, and lqmpc_last_kernel is left naming the solve kernel.
+static int rcgrad_check(const void *h, const Call &c, int T, const double *A, const double *B, const double *At, const double *Bt,
+                        const double *X, const double *Utape, const double *gJT, const double *gX, const double *gU, double *const out[7])
+{
+    if (!h || !A || !B || !At || !Bt || !X || !Utape) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (!gJT && !gX && !gU) return fail(LQMPC_ERR_BAD_ARG, "gJT, gX and gU are all NULL: there is no cotangent");
+    bool any = false;
+    for (int k = 0; k < 7; ++k) any = any || out[k];
+    if (!any) return fail(LQMPC_ERR_BAD_ARG, "every output is NULL");
+    if (T < 1 || T > 100000) return fail(LQMPC_ERR_BAD_ARG, "T must be in [1,100000]");
+    const int rc = check_call(c);
+    if (rc) return rc;
+    if (!lqmpc::rcgrad_fits(c.nx, c.nu, c.N)) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "lqmpc_rollout_cost_grad_kernel needs %zu bytes of LDS at (%d,%d,%d): over 160 KiB",
+                 lqmpc::rcgrad_lds_bytes(c.nx, c.nu, c.N), c.nx, c.nu, c.N);
+        return fail(LQMPC_ERR_UNSUPPORTED, buf);
+    }
+    return 0;
+}
+
+int lqmpc_rollout_cost_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *dA, const double *dB,
+                                      const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                                      const double *A_true, const double *B_true, int true_per_instance, const double *x_ref,
+                                      const double *u_ref, const double *dX, const double *dUtape, const int32_t *dstatus_tape,
+                                      const double *dgJT, const double *dgX, const double *dgU, int reduce, double *dgQ, double *dgR,
+                                      double *dgP, double *dglb, double *dgub, double *dgxref, double *dguref, int64_t *dnskipped)
+{
+    const bool per = true_per_instance != 0;
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, per ? nullptr : A_true, per ? nullptr : B_true,
+                 nullptr};
+    lqmpc::RCGradParams g{};
+    double *const outs[7] = {dgQ, dgR, dgP, dglb, dgub, dgxref, dguref};
+    int rc = rcgrad_check(h, c, T, dA, dB, A_true, B_true, dX, dUtape, dgJT, dgX, dgU, outs);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    rc = upload_shared(h, c, nullptr, g.so);
+    if (rc) return rc;
+    const double *sh = (const double *)h->shared.p;
+    g.nx = nx; g.nu = nu; g.N = N; g.T = T; g.Bsz = Bsz;
+    g.A = dA; g.B = dB;
+    g.At = per ? A_true : sh + g.so.At; g.Bt = per ? B_true : sh + g.so.Bt;
+    g.sE = per ? Bsz : 1; g.sI = per ? 1 : 0;
+    g.X = dX; g.Utape = dUtape; g.status_tape = dstatus_tape; g.sh = sh;
+    g.gJT = dgJT; g.gX = dgX; g.gU = dgU;
+    g.reduce = reduce ? 1 : 0;
+    for (int k = 0; k < 7; ++k) g.out[k] = outs[k];
+    g.nskipped = (long long *)dnskipped;
+    if (g.reduce) {
+        rc = ensure(h, h->rcgrad_part, lqmpc::rcgrad_part_bytes(nx, nu, N, Bsz));
+        if (rc) return rc;
+        g.part = (double *)h->rcgrad_part.p;
+    }
+    if (!lqmpc::launch_rcgrad(g, h->stream)) return fail(LQMPC_ERR_HIP, "lqmpc_rollout_cost_grad_kernel launch failed");
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int lqmpc_max_vn_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int K, const double *dA, const double *dB,
                            const double *Q, const double *R, const double *P, const double *lb, const double *ub,
                            const double *x0s, const double *x_ref, const double *u_ref, double *dMV, int32_t *dstatus,
@@ -1377,6 +1438,40 @@ int lqmpc_rollout_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz
     rc = s.upload();
     if (!rc) rc = lqmpc_rollout_grad_batch_dev(h, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dAt, dBt, true_per_instance, x_ref, u_ref, dX,
                                                dUt, dstt, dgJ, dgX, dgU, dgA, dgB, dgx, dgAt, dgBt);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_rollout_cost_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *A, const double *B,
+                                  const double *Q, const double *R, const double *P, const double *lb, const double *ub,
+                                  const double *A_true, const double *B_true, int true_per_instance, const double *x_ref,
+                                  const double *u_ref, const double *X, const double *Utape, const int32_t *status_tape,
+                                  const double *gJT, const double *gX, const double *gU, int reduce, double *gQ, double *gR, double *gP,
+                                  double *glb, double *gub, double *gxref, double *guref, int64_t *nskipped)
+{
+    const bool per = true_per_instance != 0;
+    const Call c{nx, nu, N, 0, 0, lqmpc::MODE_SOLVE, 0, Bsz, Q, R, P, lb, ub, x_ref, u_ref, per ? nullptr : A_true, per ? nullptr : B_true,
+                 nullptr};
+    double *const outs[7] = {gQ, gR, gP, glb, gub, gxref, guref};
+    int rc = rcgrad_check(h, c, T, A, B, A_true, B_true, X, Utape, gJT, gX, gU, outs);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)Bsz, cnt = reduce ? 1 : b;
+    size_t n[7];
+    cgrad_counts(nx, nu, N, n);
+    const double *dA, *dB, *dAt = A_true, *dBt = B_true, *dX, *dUt, *dgJ, *dgX, *dgU;
+    const int32_t *dstt;
+    double *d[7];
+    int64_t *dns;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB);
+    if (per) { s.in(A_true, b * nx * nx, dAt); s.in(B_true, b * nx * nu, dBt); }
+    s.in(X, b * nx * (T + 1), dX); s.in(Utape, b * nu * N * T, dUt); s.in(status_tape, b * T, dstt);
+    s.in(gJT, b, dgJ); s.in(gX, b * nx * (T + 1), dgX); s.in(gU, b * nu * T, dgU);
+    for (int k = 0; k < 7; ++k) s.out(outs[k], n[k] * cnt, d[k]);
+    s.out(reduce ? nskipped : (int64_t *)nullptr, 1, dns);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_rollout_cost_grad_batch_dev(h, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dAt, dBt, true_per_instance, x_ref, u_ref,
+                                                    dX, dUt, dstt, dgJ, dgX, dgU, reduce, d[0], d[1], d[2], d[3], d[4], d[5], d[6], dns);
     return rc ? rc : s.finish();
 }
 

@@ -173,4 +173,29 @@ size_t rgrad_lds_bytes(int nx, int nu, int N);
 bool rgrad_fits(int nx, int nu, int N);
 bool launch_rgrad(const RGradParams &p, hipStream_t stream);
 
+// lqmpc_rcgrad.hip: the gradient of the same loss on the same tape with respect to the data the batch shares -- the weights Q, R, P, the
+// box lb, ub and the references x_ref, u_ref (lqmpc_rollout_cost_grad_batch).  One launch per instance (reduce = 0: every output
+// instance-minor); with reduce every wavefront leaves one vector of partial sums in `part` and a second small kernel adds them in a
+// fixed order (every output in the shape of its parameter, row-major).
+struct RCGradParams {
+    int nx, nu, N, T;
+    long long Bsz;
+    const double *A, *B;                  // the model, instance-minor
+    const double *At, *Bt;                // the plant, as PlantStepParams
+    long long sE, sI;
+    const double *X, *Utape;              // (nx, T + 1, Bsz) and T plans (nu, N, Bsz)
+    const int *status_tape;               // (T, Bsz); 2 at any step: NaN in every output of the instance / left out of the sums; null: all 0
+    const double *sh;                     // shared block (device): Q, R, P, the box, x_ref and u_ref at the offsets so
+    SharedOff so;
+    const double *gJT, *gX, *gU;          // d loss / d J_T (Bsz), d X (nx, T + 1, Bsz), d U (nu, T, Bsz); null = zero
+    int reduce;
+    double *out[7];                       // gQ, gR, gP, glb, gub, gxref, guref; any may be null, not all
+    long long *nskipped;                  // reduce: the number of instances with status 2 at any step (device); may be null
+    double *part;                         // reduce: rcgrad_part_bytes of the handle's own block, entry e of wavefront g at part[e * blocks + g]
+};
+size_t rcgrad_lds_bytes(int nx, int nu, int N);
+bool rcgrad_fits(int nx, int nu, int N);
+size_t rcgrad_part_bytes(int nx, int nu, int N, long long Bsz);
+bool launch_rcgrad(const RCGradParams &p, hipStream_t stream);
+
 }  // namespace lqmpc

@@ -291,6 +291,37 @@ class BatchSolver:
                                                     *[_ptr(out.get(k)) for k in shapes]))
         return out
 
+    def rollout_cost_grad_batch(self, T, N, A, B, Q, R, P, lb, ub, A_true, B_true, X, U_tape, status_tape=None, g_JT=None, g_X=None,
+                                g_U=None, x_ref=None, u_ref=None, reduce=False):
+        """The gradient of a loss on the closed loop with respect to the data the batch shares -- the weights, the references and the
+        box -- from the tape of rollout_tape_batch (lqmpc_rollout_cost_grad_batch); arguments as rollout_grad_batch.  Returns the dict
+        of cost_grad_batch: {"g_Q", "g_R", "g_P", "g_lb", "g_ub", "g_xref", "g_uref"} per instance with the instance axis last, or with
+        reduce=True the sum over the batch in the shape of the parameter, formed on the GPU in a fixed order, and "skipped", the
+        number of instances with status 2 at any step, which add nothing.  g_Q and g_R hold the direct part as well (the one Q and R
+        also weigh J_T); for the controller's weights alone under fixed evaluation weights pass g_JT=None and put the evaluation cost
+        into g_X and g_U.  g_Q, g_R, g_P take the entries of the matrix as independent: nothing is symmetrised.  One kernel launch
+        (two with reduce), no solve."""
+        A, B, nx, nu, Bsz = self._dims(A, B)
+        Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
+        lb, ub = _f64(lb, (nu,)), _f64(ub, (nu,))
+        A_true, B_true, per_inst = self._plant(A_true, B_true, nx, nu, Bsz)
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        X, U_tape = _f64(X, (nx, T + 1, Bsz)), _f64(U_tape, (T, nu, N, Bsz))
+        status_tape = None if status_tape is None else np.ascontiguousarray(status_tape, dtype=np.int32).reshape(T, Bsz)
+        g_JT = None if g_JT is None else _f64(g_JT, (Bsz,))
+        g_X = None if g_X is None else _f64(g_X, (nx, T + 1, Bsz))
+        g_U = None if g_U is None else _f64(g_U, (nu, T, Bsz))
+        out = _cgrad_outputs(nx, nu, N, Bsz, reduce)
+        skipped = np.zeros(1, dtype=np.int64)
+        _lib.check(self._L.lqmpc_rollout_cost_grad_batch(self._h, nx, nu, N, Bsz, T, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P),
+                                                         _ptr(lb), _ptr(ub), _ptr(A_true), _ptr(B_true), per_inst, _ptr(x_ref),
+                                                         _ptr(u_ref), _ptr(X), _ptr(U_tape), _ptr(status_tape), _ptr(g_JT), _ptr(g_X),
+                                                         _ptr(g_U), int(bool(reduce)), *[_ptr(out[k]) for k in _CGRAD_KEYS],
+                                                         _ptr(skipped)))
+        if reduce:
+            out["skipped"] = int(skipped[0])
+        return out
+
     def max_vn_batch(self, N, A, B, Q, R, P, lb, ub, x0s, x_ref=None, u_ref=None):
         A, B, nx, nu, Bsz = self._dims(A, B)
         Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
@@ -518,6 +549,21 @@ class BatchSolver:
                                                         _ptr(x_ref), _ptr(u_ref), _ptr(dX), _ptr(dUtape), _ptr(dstatus_tape), _ptr(dgJT),
                                                         _ptr(dgX), _ptr(dgU), _ptr(dgA), _ptr(dgB), _ptr(dgx0), _ptr(dgA_true),
                                                         _ptr(dgB_true)))
+
+    def rollout_cost_grad_batch_dev(self, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, A_true, B_true, dX, dUtape, outs, dstatus_tape=None,
+                                    dgJT=None, dgX=None, dgU=None, true_per_instance=False, x_ref=None, u_ref=None, reduce=False,
+                                    dskipped=None):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_rollout_cost_grad_batch_dev).  outs: a
+        dict with any of the keys g_Q, g_R, g_P, g_lb, g_ub, g_xref, g_uref (at least one); dskipped: an int64 device scalar."""
+        Q, R, P, lb, ub = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), _f64(lb, (nu,)), _f64(ub, (nu,))
+        if not true_per_instance:
+            A_true, B_true = _f64(A_true, (nx, nx)), _f64(B_true, (nx, nu))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        _lib.check(self._L.lqmpc_rollout_cost_grad_batch_dev(self._h, nx, nu, N, Bsz, T, _ptr(dA), _ptr(dB), _ptr(Q), _ptr(R), _ptr(P),
+                                                             _ptr(lb), _ptr(ub), _ptr(A_true), _ptr(B_true),
+                                                             1 if true_per_instance else 0, _ptr(x_ref), _ptr(u_ref), _ptr(dX),
+                                                             _ptr(dUtape), _ptr(dstatus_tape), _ptr(dgJT), _ptr(dgX), _ptr(dgU),
+                                                             int(bool(reduce)), *_cgrad_dev_ptrs(outs), _ptr(dskipped)))
 
     def max_vn_batch_dev(self, nx, nu, N, Bsz, dA, dB, Q, R, P, lb, ub, x0s, dMV, dstatus=None, diters=None,
                          x_ref=None, u_ref=None):

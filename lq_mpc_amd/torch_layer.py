@@ -11,6 +11,8 @@
     loss(Uplan, Xplan, VN).backward()                    # x.grad, A.grad, B.grad for a loss on every u_i, every x_i and V_N
     JT, X, U = layer.rollout(x0, T, A_true, B_true)      # the closed loop of T steps on the plant A_true, B_true; A, B optional
     loss(JT, X, U).backward()                            # x0.grad, A_true.grad, B_true.grad (with A, B: theirs too) through the whole loop
+    JT, X, U = layer.rollout(x0, T, A_true, B_true, Q=Q, lb=lb)   # ... under weights, a box or references given as fp64 CPU tensors
+    loss(JT, X, U).backward()                            # Q.grad, lb.grad (any of Q, R, P, lb, ub, x_ref, u_ref), summed over the batch
 
 Forward is one lqmpc_controller_step_sens_dev on the tensors' own pointers: the QP of every instance, then the post-pass that returns
 K_0 = d u_0 / d x and dV_N / d x on the face the plan ends on.  Backward is  grad_x = K_0' grad_u0 + dV_dx grad_VN, a torch einsum.
@@ -32,8 +34,9 @@ was made under.
 
 The law of a box-constrained MPC is piecewise affine: the gradient is that of the critical region x lies in, exact inside it and
 one-sided on its border.  The model (A, B) is differentiated per instance and the references for the batch as a whole.  The weights
-and the box are fixed when the controller is made, so the layer does not differentiate them: their gradients are those of
-BatchController.cost_grad and BatchSolver.cost_grad_batch.
+and the box are fixed when the controller is made, so the step does not differentiate them: their gradients are those of
+BatchController.cost_grad and BatchSolver.cost_grad_batch.  layer.rollout runs on the batch calls, not on the controller, and takes
+all seven with the call (its docstring).
 """
 import numpy as np
 import torch
@@ -257,6 +260,71 @@ class _MPCRollout(torch.autograd.Function):
         return g_x, g_A, g_B, g_At, g_Bt, None, None
 
 
+class _MPCRolloutShared(torch.autograd.Function):
+    """the closed loop under weights, a box or references given with the call: differentiable in them (summed over the batch) as well
+    as in x0, the model and the plant"""
+
+    KEYS = ("g_Q", "g_R", "g_P", "g_lb", "g_ub", "g_xref", "g_uref")
+
+    @staticmethod
+    def forward(ctx, x0, A, B, At, Bt, Q, R, P, lb, ub, x_ref, u_ref, layer, T):
+        ctl = layer.controller
+        nx, nu, N, Bsz = ctl.nx, ctl.nu, ctl.N, ctl.Bsz
+        if x0.dtype != torch.float64 or not x0.is_cuda or tuple(x0.shape) != (nx, Bsz):
+            raise ValueError(f"x0 must be a float64 device tensor of shape ({nx}, {Bsz})")
+        for M, shape in ((A, (nx, nx, Bsz)), (B, (nx, nu, Bsz)), (At, (nx, nx, Bsz)), (Bt, (nx, nu, Bsz))):
+            if M.dtype != torch.float64 or not M.is_cuda or tuple(M.shape) != shape:
+                raise ValueError(f"the model and the plant must be float64 device tensors of shapes ({nx}, {nx}, {Bsz}) and ({nx}, {nu}, {Bsz})")
+        given = (Q, R, P, lb, ub, x_ref, u_ref)
+        shapes = ((nx, nx), (nu, nu), (nx, nx), (nu,), (nu,), (nx, N), (nu, N))
+        for M, shape in zip(given, shapes):
+            if M is not None and (M.dtype != torch.float64 or M.is_cuda or tuple(M.shape) != shape):
+                raise ValueError("Q, R, P, lb, ub, x_ref and u_ref must be float64 CPU tensors of the shapes of the layer's own")
+        own = layer._shared + (layer._refs["x_ref"], layer._refs["u_ref"])
+        data = tuple(o if M is None else M.detach().contiguous().numpy().copy() for M, o in zip(given, own))
+        shared, refs = data[:5], dict(x_ref=data[5], u_ref=data[6])
+        x0, A, B, At, Bt = (M.detach().contiguous() for M in (x0, A, B, At, Bt))
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=x0.device)
+        JT, X, U, Ut = new(Bsz), new(nx, T + 1, Bsz), new(nu, T, Bsz), new(T, nu, N, Bsz)
+        st = torch.empty((T, Bsz), dtype=torch.int32, device=x0.device)
+        layer.solver.rollout_tape_batch_dev(nx, nu, N, Bsz, T, A, B, *shared, x0, At, Bt, JT, Ut, dX=X, dU=U, dstatus_tape=st,
+                                            true_per_instance=True, **refs)
+        ctx.save_for_backward(A, B, At, Bt, X, Ut, st)
+        ctx.layer, ctx.T, ctx.shared, ctx.refs, ctx.shapes = layer, T, shared, refs, shapes
+        return JT, X, U
+
+    @staticmethod
+    def backward(ctx, grad_J, grad_X, grad_U):
+        A, B, At, Bt, X, Ut, st = ctx.saved_tensors
+        layer, T = ctx.layer, ctx.T
+        none = (None,) * 14
+        if grad_J is None and grad_X is None and grad_U is None:
+            return none
+        ctl = layer.controller
+        nx, nu, N, Bsz = ctl.nx, ctl.nu, ctl.N, ctl.Bsz
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=X.device)
+        need = ctx.needs_input_grad
+        cot = [None if g is None else g.contiguous() for g in (grad_J, grad_X, grad_U)]
+        g_x = g_A = g_B = g_At = g_Bt = None
+        if any(need[:5]):
+            g_x = new(nx, Bsz)
+            g_A = new(nx, nx, Bsz) if need[1] else None
+            g_B = new(nx, nu, Bsz) if need[2] else None
+            g_At = new(nx, nx, Bsz) if need[3] else None
+            g_Bt = new(nx, nu, Bsz) if need[4] else None
+            layer.solver.rollout_grad_batch_dev(nx, nu, N, Bsz, T, A, B, *ctx.shared, At, Bt, X, Ut, dstatus_tape=st, dgJT=cot[0],
+                                                dgX=cot[1], dgU=cot[2], dgA=g_A, dgB=g_B, dgx0=g_x, dgA_true=g_At, dgB_true=g_Bt,
+                                                true_per_instance=True, **ctx.refs)
+        g_shared = [None] * 7
+        if any(need[5:12]):
+            outs = {k: new(*shape) for k, shape, n in zip(_MPCRolloutShared.KEYS, ctx.shapes, need[5:12]) if n}
+            layer.solver.rollout_cost_grad_batch_dev(nx, nu, N, Bsz, T, A, B, *ctx.shared, At, Bt, X, Ut, outs, dstatus_tape=st, dgJT=cot[0],
+                                                     dgX=cot[1], dgU=cot[2], true_per_instance=True, reduce=True, **ctx.refs)
+            # the shared data live on the host: the one wait for the host on this path
+            g_shared = [outs[k].cpu() if k in outs else None for k in _MPCRolloutShared.KEYS]
+        return (g_x, g_A, g_B, g_At, g_Bt, *g_shared, None, None)
+
+
 class MPCLayer(torch.nn.Module):
     """u0, VN = MPCLayer(N, A, B, Q, R, P, lb, ub)(x) around a BatchController; options are the solver's (BatchSolver.set_options).
     layer(x, A, B) steps under the models A, B (they become the controller's) and is differentiable in them as well;
@@ -275,14 +343,20 @@ class MPCLayer(torch.nn.Module):
         self._shared = tuple(np.ascontiguousarray(M, dtype=np.float64) for M in (Q, R, P, lb, ub))
         self._refs = dict(x_ref=x_ref, u_ref=u_ref)
 
-    def rollout(self, x0, T, A_true, B_true, A=None, B=None):
+    def rollout(self, x0, T, A_true, B_true, A=None, B=None, *, Q=None, R=None, P=None, lb=None, ub=None, x_ref=None, u_ref=None):
         """J_T (Bsz,), X (nx, T + 1, Bsz), U (nu, T, Bsz) of the closed loop of T steps from x0 (nx, Bsz): the model drives every QP
         -- A, B where given, else those the layer was made with -- and the plant A_true, B_true drives the state: (nx, nx), (nx, nu)
         shared by the batch or (nx, nx, Bsz), (nx, nu, Bsz).  Differentiable in x0, A, B, A_true and B_true for a loss on all three
         outputs.  Forward is one lqmpc_rollout_tape_batch_dev (T plan calls with a plant step behind each: not the fast rollout),
         backward one lqmpc_rollout_grad_batch_dev (csrc/lqmpc_rgrad.hip) on the tape it left; a shared plant is expanded over the
-        batch in torch, so its gradient is summed by autograd.  The weights, the box and the references are those the layer was made
-        with.  Nothing waits for the host."""
+        batch in torch, so its gradient is summed by autograd.  Nothing waits for the host.
+        Any of Q, R, P, lb, ub, x_ref, u_ref may be given as a float64 CPU tensor (the data the batch shares are host data, as
+        everywhere in the library): the loop then runs under them for this call, one left out is the layer's own, and one that
+        requires grad gets the gradient summed over the batch, from one lqmpc_rollout_cost_grad_batch_dev with reduce
+        (csrc/lqmpc_rcgrad.hip) and a copy of the small results to the host, the one wait for the host on this path.  Q and R weigh
+        J_T as well as the QP, and their gradients hold both parts.  Q.grad, R.grad and P.grad take the entries of the matrix as
+        independent: a caller who parametrises a symmetric Q gets <Q.grad, dQ> through autograd, and nothing is symmetrised on their
+        behalf.  With none of the seven given the call runs exactly the launches it ran before they could be."""
         if (A is None) != (B is None):
             raise ValueError("give both A and B, or neither")
         ctl = self.controller
@@ -294,7 +368,9 @@ class MPCLayer(torch.nn.Module):
         for M in (A_true, B_true):
             M = M.to(x0.device)
             plant.append(M.unsqueeze(-1).expand(*M.shape, ctl.Bsz) if M.dim() == 2 else M)
-        return _MPCRollout.apply(x0, A, B, plant[0], plant[1], self, int(T))
+        if all(M is None for M in (Q, R, P, lb, ub, x_ref, u_ref)):
+            return _MPCRollout.apply(x0, A, B, plant[0], plant[1], self, int(T))
+        return _MPCRolloutShared.apply(x0, A, B, plant[0], plant[1], Q, R, P, lb, ub, x_ref, u_ref, self, int(T))
 
     def forward(self, x, A=None, B=None, *, x_ref=None, u_ref=None):
         if (A is None) != (B is None):
