@@ -528,6 +528,70 @@ int lqmpc_rollout_cost_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, in
                                       double *dgQ, double *dgR, double *dgP, double *dglb, double *dgub, double *dgxref,
                                       double *dguref, int64_t *dnskipped);
 
+/* ---- polytopic input constraints: F_u u_i <= 1 for ANY matrix F_u (utils_class.py:81), not only the rows of a box ----
+ * Per instance, with n = N nu and no 1/2 factor, as everywhere in this header:
+ *     min  sum_{i=0}^{N-2} |x_{i+1} - xref_i|^2_Q + |x_N - xref_{N-1}|^2_P + sum_{i=0}^{N-1} |u_i - uref_i|^2_R
+ *     s.t. x_{i+1} = A x_i + B u_i,   Fu u_i <= 1  (componentwise, i = 0..N-1);     u_0 = u*[:, 0],  V_N = cost* + x0'Q x0.
+ * Fu is (m, nu), row-major, a HOST pointer shared by the batch and copied by the call, like Q, R, lb, ub.  u = 0 is strictly feasible
+ * and R > 0, so the QP is feasible and strictly convex: "infeasible" cannot occur.  The polytope need not be bounded (one row
+ * [[10.]] is a one-sided limit).  rho = max_j 1 / |Fu_j|_2, the distance of the farthest facet, stands where the box calls have the
+ * half-width h.
+ * METHOD: Goldfarb-Idnani, the dual active-set method from the unconstrained minimiser, on the rows normalised to unit length; exact and
+ * finite, and it copes with dependent active rows (m > nu).  One instance per wavefront, one launch: lqmpc_last_kernel names
+ * lqmpc_poly_solve_kernel / lqmpc_poly_rollout_kernel.  No options but eps are read: a row counts as satisfied within eps * rho.
+ * DOMAIN: nx <= 16, nu <= LQMPC_MAX_NU, N <= LQMPC_MAX_N, n = N nu <= 64, 1 <= m <= 16, LDS image within 160 KiB (every shape of the
+ * domain fits).  Outside: LQMPC_ERR_UNSUPPORTED with a message that names the domain; there is no fall-back to another kernel family.
+ * LQMPC_ERR_BAD_ARG: m < 1, a NULL Fu, a row of Fu that is all zero or holds a non-finite entry, max_iter < 0, the usual NULL or size
+ * errors.  Every refusal happens before anything is enqueued, from the arguments alone.
+ * max_iter caps the passes (adds + drops) of one solve; 0 = 10 n + 20 (measured: at most 193 at n = 64 with a 16-gon, 43 at (4,2,10) with an octagon).  No loop of the
+ * kernel depends on the data for its termination.
+ * OUTPUTS of solve, instance-minor; u0 and VN are required, the others may be NULL, and leaving one out leaves the others bit for bit:
+ *     u0[k*Bsz + b], VN[b];  Uplan[(k*N + i)*Bsz + b] = u_i[k] (Uplan[:, 0] is u0 bit for bit);  Xplan[(a*(N+1) + i)*Bsz + b] = x_i[a],
+ *     the model's states under that plan (Xplan[:, 0] is x0 bit for bit; V_N is the cost of this roll);
+ *     lam[(j*N + i)*Bsz + b] >= 0, the multiplier of row j at stage i of the rows AS GIVEN, of the Lagrangian
+ *     V(U) + sum lam_ij (Fu_j u_i - 1):  2 (H U + g) + C'lam = 0 with C = I_N (x) Fu.  Where active rows depend on each other (a vertex
+ *     with more than nu rows through it) the multipliers are one valid choice; the plan is unique.
+ *     status[b]: 0 optimal; 1 max_iter reached, or no step left -- the outputs are the last iterate of a DUAL method, which may
+ *     violate rows; 2 non-finite data (the outputs of that instance are not numbers; the other instances are untouched).
+ *     iters[b] = adds + drops.
+ * ACCURACY, on models with cond_2(H) <= 53 (tests/test_gpu_poly.py, against a long-double reference): |U - U*| <= 1e-10 max(|U*|, rho)
+ * for the whole plan, |V_N - V_N*| <= 1e-11 V_N*, every row Fu_j u_i - 1 <= 1e-10, lam >= 0 exactly and > 0 only on rows within 1e-10
+ * of equality, stationarity within 1e-10 (|2H| max(|U|, rho) + |2g|).
+ * rollout: T closed-loop steps in one launch from one set-up, as lqmpc_rollout_batch: u_t = u_0 of the QP at x_t (cold start, from a
+ * pristine factor at every step that follows a step with an add, so rounding does not accumulate over T), x_{t+1} = A_true x_t +
+ * B_true u_t, J_T = x_0'Q x_0 + sum_t (x_{t+1}'Q x_{t+1} + u_t'R u_t) summed in that order; X (nx, T+1, Bsz) and U (nu, T, Bsz) may be
+ * NULL; status = the largest over the steps, iters = the sum; T in [1, 100000]; A_true / B_true shared (host) or per instance.
+ * NOT HERE: the prepared controller, the sens / grad / tape calls, sweep, max_vn and the bound coefficients for a polytope; n > 64; a
+ * per-instance Fu; state constraints; warm start across rollout steps. */
+int lqmpc_solve_poly_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                           const double *A, const double *B,
+                           const double *Q, const double *R, const double *P,
+                           const double *Fu, int m, const double *x0,
+                           const double *x_ref, const double *u_ref, int max_iter,
+                           double *u0, double *VN, double *Uplan, double *Xplan, double *lam,
+                           int32_t *status, int32_t *iters);
+int lqmpc_solve_poly_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                               const double *dA, const double *dB,
+                               const double *Q, const double *R, const double *P,
+                               const double *Fu, int m, const double *dx0,
+                               const double *x_ref, const double *u_ref, int max_iter,
+                               double *du0, double *dVN, double *dUplan, double *dXplan, double *dlam,
+                               int32_t *dstatus, int32_t *diters);
+int lqmpc_rollout_poly_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T,
+                             const double *A, const double *B,
+                             const double *Q, const double *R, const double *P,
+                             const double *Fu, int m, const double *x0,
+                             const double *A_true, const double *B_true, int true_per_instance,
+                             const double *x_ref, const double *u_ref, int max_iter,
+                             double *JT, double *X, double *U, int32_t *status, int32_t *iters);
+int lqmpc_rollout_poly_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T,
+                                 const double *dA, const double *dB,
+                                 const double *Q, const double *R, const double *P,
+                                 const double *Fu, int m, const double *dx0,
+                                 const double *A_true, const double *B_true, int true_per_instance,
+                                 const double *x_ref, const double *u_ref, int max_iter,
+                                 double *dJT, double *dX, double *dU, int32_t *dstatus, int32_t *diters);
+
 /* ---- M_V = max_k V_N(x0s[:,k]) per instance (utils_class.py:816-824, 899-907) ---- */
 int lqmpc_max_vn_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int K,
                        const double *A, const double *B,

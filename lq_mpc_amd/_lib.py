@@ -43,6 +43,7 @@ EXPORTS = [
     "lqmpc_plan_grad_batch", "lqmpc_plan_grad_batch_dev", "lqmpc_controller_plan_grad", "lqmpc_controller_plan_grad_dev",
     "lqmpc_rollout_tape_batch", "lqmpc_rollout_tape_batch_dev", "lqmpc_rollout_grad_batch", "lqmpc_rollout_grad_batch_dev",
     "lqmpc_rollout_cost_grad_batch", "lqmpc_rollout_cost_grad_batch_dev",
+    "lqmpc_solve_poly_batch", "lqmpc_solve_poly_batch_dev", "lqmpc_rollout_poly_batch", "lqmpc_rollout_poly_batch_dev",
 ]
 
 
@@ -123,6 +124,12 @@ def lib():
     rcgrad_args = dims + [ctypes.c_int] + [P] * 9 + [ctypes.c_int] + [P] * 8 + [ctypes.c_int] + [P] * 8
     L.lqmpc_rollout_cost_grad_batch.argtypes = rcgrad_args
     L.lqmpc_rollout_cost_grad_batch_dev.argtypes = rcgrad_args
+    poly_args = dims + [P] * 6 + [ctypes.c_int] + [P] * 3 + [ctypes.c_int] + [P] * 7
+    L.lqmpc_solve_poly_batch.argtypes = poly_args
+    L.lqmpc_solve_poly_batch_dev.argtypes = poly_args
+    poly_roll_args = dims + [ctypes.c_int] + [P] * 6 + [ctypes.c_int] + [P] * 3 + [ctypes.c_int] + [P] * 2 + [ctypes.c_int] + [P] * 5
+    L.lqmpc_rollout_poly_batch.argtypes = poly_roll_args
+    L.lqmpc_rollout_poly_batch_dev.argtypes = poly_roll_args
     mv_args = dims + [ctypes.c_int] + [P] * 13
     L.lqmpc_max_vn_batch.argtypes = mv_args
     L.lqmpc_max_vn_batch_dev.argtypes = mv_args

@@ -399,6 +399,8 @@ static int check_call(const Call &c)
     return 0;
 }
 
+static int upload_block(lqmpc_handle *h, std::vector<double> &sh);
+
 // Pack the batch-shared data of a call (Kg: the first gain of an order's roll key, or null = zeros) and upload it, skipped when
 // identical to the last upload; `so` takes the offsets.  The block of a post-pass is the block of the solve it follows, bit for bit.
 static int upload_shared(lqmpc_handle *h, const Call &c, const double *Kg, lqmpc::SharedOff &so)
@@ -422,6 +424,12 @@ static int upload_shared(lqmpc_handle *h, const Call &c, const double *Kg, lqmpc
     so.Bt = put(c.true_per_instance ? nullptr : c.Bt_sh, nx * nu);
     so.x0s = put(c.x0s, c.x0s ? nx * c.K : 1);
     so.Kg = put(Kg, nu * nx);
+    return upload_block(h, sh);
+}
+
+// The packed shared block of a call on its way to the device, skipped when identical to the last upload.
+static int upload_block(lqmpc_handle *h, std::vector<double> &sh)
+{
     int rc = ensure(h, h->shared, sh.size() * sizeof(double));
     if (rc) return rc;
     if (sh != h->shared_host) {
@@ -1091,6 +1099,114 @@ int lqmpc_rollout_cost_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, in
     return 0;
 }
 
+}  // extern "C"
+
+// ---- polytopic input constraints Fu u <= 1 (lqmpc_poly.hip) ----
+constexpr int POLY_MAX_NVAR = 64, POLY_MAX_ROWS = 16;
+
+// Every refusal of a polytope call, from the arguments alone: the handle is not dereferenced, nothing is enqueued.
+static int poly_check(const void *h, int nx, int nu, int N, int64_t Bsz, int T, bool roll, const double *A, const double *B, const double *Q,
+                      const double *R, const double *P, const double *Fu, int m, const double *x0, const double *At, const double *Bt,
+                      int max_iter, const void *out0, const void *out1)
+{
+    int rc = check_dims(nx, nu, N, Bsz);
+    if (rc) return rc;
+    if (m < 1) return fail(LQMPC_ERR_BAD_ARG, "m must be positive: Fu needs at least one row");
+    if (N * nu > POLY_MAX_NVAR || m > POLY_MAX_ROWS || !lqmpc::poly_fits(nx, nu, N, m)) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "the polytope kernels serve nx<=%d, nu<=%d, N<=%d, N*nu<=%d, 1<=m<=%d and an LDS image within 160 KiB; "
+                 "(%d,%d,%d) with m=%d (LDS %zu bytes) is outside", LQMPC_MAX_NX, LQMPC_MAX_NU, LQMPC_MAX_N, POLY_MAX_NVAR, POLY_MAX_ROWS,
+                 nx, nu, N, m, m <= POLY_MAX_ROWS ? lqmpc::poly_lds_bytes(nx, nu, N, m) : (size_t)0);
+        return fail(LQMPC_ERR_UNSUPPORTED, buf);
+    }
+    if (!h || !A || !B || !x0 || !out0 || !out1 || (roll && (!At || !Bt))) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (!Q || !R || !P || !Fu) return fail(LQMPC_ERR_BAD_ARG, "Q, R, P, Fu must not be NULL");
+    if (roll && (T < 1 || T > 100000)) return fail(LQMPC_ERR_BAD_ARG, "T must be in [1,100000]");
+    if (max_iter < 0) return fail(LQMPC_ERR_BAD_ARG, "max_iter must be >= 0 (0: 10 N nu + 20)");
+    for (int j = 0; j < m; ++j) {
+        bool zero = true;
+        for (int k = 0; k < nu; ++k) {
+            if (!std::isfinite(Fu[j * nu + k])) {
+                char buf[96];
+                snprintf(buf, sizeof buf, "row %d of Fu holds a non-finite entry", j);
+                return fail(LQMPC_ERR_BAD_ARG, buf);
+            }
+            zero = zero && Fu[j * nu + k] == 0.0;
+        }
+        if (zero) {
+            char buf[96];
+            snprintf(buf, sizeof buf, "row %d of Fu is all zero", j);
+            return fail(LQMPC_ERR_BAD_ARG, buf);
+        }
+    }
+    return 0;
+}
+
+// The shared block of a polytope call, the parameter block and the one launch.
+static int poly_run(lqmpc_handle *h, lqmpc::PolyParams &p, const double *Q, const double *R, const double *P, const double *Fu,
+                    const double *x_ref, const double *u_ref, const double *At_sh, const double *Bt_sh)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    const int nx = p.nx, nu = p.nu, N = p.N;
+    std::vector<double> sh;
+    auto put = [&](const double *src, int count) {
+        int off = (int)sh.size();
+        sh.resize(sh.size() + count, 0.0);
+        if (src) memcpy(sh.data() + off, src, sizeof(double) * count);
+        return off;
+    };
+    p.so.Q = put(Q, nx * nx);
+    p.so.R = put(R, nu * nu);
+    p.so.P = put(P, nx * nx);
+    p.so.Fu = put(Fu, p.m * nu);
+    p.so.xref = put(x_ref, nx * N);
+    p.so.uref = put(u_ref, nu * N);
+    p.so.At = put(At_sh, nx * nx);
+    p.so.Bt = put(Bt_sh, nx * nu);
+    const int rc = upload_block(h, sh);
+    if (rc) return rc;
+    p.sh = (const double *)h->shared.p;
+    if (At_sh) { p.At = p.sh + p.so.At; p.Bt = p.sh + p.so.Bt; p.sE = 1; p.sI = 0; }
+    p.eps = h->opt.eps;
+    const char *name = nullptr;
+    if (!lqmpc::launch_poly(p, h->stream, &name)) return fail(LQMPC_ERR_HIP, "the polytope kernel's launch failed");
+    HIP_TRY(hipGetLastError());
+    set_last_kernel(h, name);
+    return 0;
+}
+
+extern "C" {
+
+int lqmpc_solve_poly_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *dA, const double *dB, const double *Q,
+                               const double *R, const double *P, const double *Fu, int m, const double *dx0, const double *x_ref,
+                               const double *u_ref, int max_iter, double *du0, double *dVN, double *dUplan, double *dXplan, double *dlam,
+                               int32_t *dstatus, int32_t *diters)
+{
+    const int rc = poly_check(h, nx, nu, N, Bsz, 0, false, dA, dB, Q, R, P, Fu, m, dx0, nullptr, nullptr, max_iter, du0, dVN);
+    if (rc) return rc;
+    lqmpc::PolyParams p{};
+    p.nx = nx; p.nu = nu; p.N = N; p.m = m; p.T = 0; p.max_iter = max_iter; p.Bsz = Bsz;
+    p.A = dA; p.B = dB; p.x0 = dx0;
+    p.u0 = du0; p.VN = dVN; p.Uplan = dUplan; p.Xplan = dXplan; p.lam = dlam; p.status = dstatus; p.iters = diters;
+    return poly_run(h, p, Q, R, P, Fu, x_ref, u_ref, nullptr, nullptr);
+}
+
+int lqmpc_rollout_poly_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *dA, const double *dB,
+                                 const double *Q, const double *R, const double *P, const double *Fu, int m, const double *dx0,
+                                 const double *A_true, const double *B_true, int true_per_instance, const double *x_ref,
+                                 const double *u_ref, int max_iter, double *dJT, double *dX, double *dU, int32_t *dstatus, int32_t *diters)
+{
+    const int rc = poly_check(h, nx, nu, N, Bsz, T, true, dA, dB, Q, R, P, Fu, m, dx0, A_true, B_true, max_iter, dJT, dJT);
+    if (rc) return rc;
+    const bool per = true_per_instance != 0;
+    lqmpc::PolyParams p{};
+    p.nx = nx; p.nu = nu; p.N = N; p.m = m; p.T = T; p.max_iter = max_iter; p.Bsz = Bsz;
+    p.A = dA; p.B = dB; p.x0 = dx0;
+    p.At = A_true; p.Bt = B_true; p.sE = Bsz; p.sI = 1;       // per instance; poly_run points a shared plant into the shared block
+    p.JT = dJT; p.X = dX; p.U = dU; p.status = dstatus; p.iters = diters;
+    return poly_run(h, p, Q, R, P, Fu, x_ref, u_ref, per ? nullptr : A_true, per ? nullptr : B_true);
+}
+
 int lqmpc_max_vn_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int K, const double *dA, const double *dB,
                            const double *Q, const double *R, const double *P, const double *lb, const double *ub,
                            const double *x0s, const double *x_ref, const double *u_ref, double *dMV, int32_t *dstatus,
@@ -1472,6 +1588,50 @@ int lqmpc_rollout_cost_grad_batch(lqmpc_handle *h, int nx, int nu, int N, int64_
     rc = s.upload();
     if (!rc) rc = lqmpc_rollout_cost_grad_batch_dev(h, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dAt, dBt, true_per_instance, x_ref, u_ref,
                                                     dX, dUt, dstt, dgJ, dgX, dgU, reduce, d[0], d[1], d[2], d[3], d[4], d[5], d[6], dns);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_solve_poly_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B, const double *Q,
+                           const double *R, const double *P, const double *Fu, int m, const double *x0, const double *x_ref,
+                           const double *u_ref, int max_iter, double *u0, double *VN, double *Uplan, double *Xplan, double *lam,
+                           int32_t *status, int32_t *iters)
+{
+    int rc = poly_check(h, nx, nu, N, Bsz, 0, false, A, B, Q, R, P, Fu, m, x0, nullptr, nullptr, max_iter, u0, VN);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)Bsz;
+    const double *dA, *dB, *dx0;
+    double *du0, *dVN, *dUp, *dXp, *dlam;
+    int32_t *dst, *dit;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(x0, b * nx, dx0);
+    s.out(u0, b * nu, du0); s.out(VN, b, dVN); s.out(Uplan, b * nu * N, dUp); s.out(Xplan, b * nx * (N + 1), dXp);
+    s.out(lam, b * m * N, dlam); s.out(status, b, dst); s.out(iters, b, dit);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_solve_poly_batch_dev(h, nx, nu, N, Bsz, dA, dB, Q, R, P, Fu, m, dx0, x_ref, u_ref, max_iter, du0, dVN, dUp, dXp, dlam,
+                                             dst, dit);
+    return rc ? rc : s.finish();
+}
+
+int lqmpc_rollout_poly_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int T, const double *A, const double *B,
+                             const double *Q, const double *R, const double *P, const double *Fu, int m, const double *x0,
+                             const double *A_true, const double *B_true, int true_per_instance, const double *x_ref,
+                             const double *u_ref, int max_iter, double *JT, double *X, double *U, int32_t *status, int32_t *iters)
+{
+    int rc = poly_check(h, nx, nu, N, Bsz, T, true, A, B, Q, R, P, Fu, m, x0, A_true, B_true, max_iter, JT, JT);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)Bsz;
+    const double *dA, *dB, *dx0, *dAt = A_true, *dBt = B_true;
+    double *dJT, *dX, *dU;
+    int32_t *dst, *dit;
+    s.in(A, b * nx * nx, dA); s.in(B, b * nx * nu, dB); s.in(x0, b * nx, dx0);
+    if (true_per_instance) { s.in(A_true, b * nx * nx, dAt); s.in(B_true, b * nx * nu, dBt); }
+    s.out(JT, b, dJT); s.out(X, b * nx * (T + 1), dX); s.out(U, b * nu * T, dU); s.out(status, b, dst); s.out(iters, b, dit);
+    rc = s.upload();
+    if (!rc) rc = lqmpc_rollout_poly_batch_dev(h, nx, nu, N, Bsz, T, dA, dB, Q, R, P, Fu, m, dx0, dAt, dBt, true_per_instance, x_ref,
+                                               u_ref, max_iter, dJT, dX, dU, dst, dit);
     return rc ? rc : s.finish();
 }
 

@@ -198,4 +198,28 @@ bool rcgrad_fits(int nx, int nu, int N);
 size_t rcgrad_part_bytes(int nx, int nu, int N, long long Bsz);
 bool launch_rcgrad(const RCGradParams &p, hipStream_t stream);
 
+// lqmpc_poly.hip: the problem with polytopic input constraints Fu u_i <= 1 (lqmpc_solve_poly_batch, lqmpc_rollout_poly_batch): one
+// solve per instance (T = 0) or T closed-loop steps from one set-up (T >= 1), one instance per wavefront.  Run-time dimensions within
+// N nu <= 64, m <= 16; poly_fits says whether the LDS image does (launch_poly refuses, and launches nothing, where not).
+struct PolyOff {
+    int Q, R, P, Fu, xref, uref, At, Bt;  // offsets (in doubles) into the shared block of a polytope call; Fu is (m, nu) row-major
+};
+struct PolyParams {
+    int nx, nu, N, m, T;
+    int max_iter;                         // cap on the passes of the active-set loop of one solve; 0: 10 N nu + 20
+    double eps;                           // a row counts as satisfied within eps * rho, rho = max_j 1 / |Fu_j|
+    long long Bsz;
+    const double *A, *B, *x0;             // instance-minor (device)
+    const double *At, *Bt;                // T >= 1: element e of the plant of instance b at At[e * sE + b * sI], as PlantStepParams
+    long long sE, sI;
+    const double *sh;                     // shared block (device)
+    PolyOff so;
+    double *u0, *VN, *Uplan, *Xplan, *lam;   // T = 0: u0 and VN required, the others may be null
+    double *JT, *X, *U;                   // T >= 1: JT required, X and U may be null
+    int *status, *iters;                  // may be null
+};
+size_t poly_lds_bytes(int nx, int nu, int N, int m);
+bool poly_fits(int nx, int nu, int N, int m);
+bool launch_poly(const PolyParams &p, hipStream_t stream, const char **name);
+
 }  // namespace lqmpc

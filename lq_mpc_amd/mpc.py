@@ -10,6 +10,8 @@ batched entry points a GPU needs (the reference API is one instance per call):
     BatchSolver.solve_batch / rollout_batch / max_vn_batch  over instance-minor (SoA) arrays,
     BatchController(solver, ...).step(x): the set-up kept on the GPU, one QP per instance and call.
 solve_batch and step return the whole optimal plan as well with want_plan=True (the reference's controller.u.value).
+An F_u that is not a box (a row with two or more non-zeros) goes through BatchSolver.solve_poly_batch / rollout_poly_batch; the two
+classes pick those calls by themselves.
 Everything executes in the HIP library behind include/lqmpc.h; there is no CPU path here.
 """
 import ctypes
@@ -40,6 +42,13 @@ def box_from_Fu(F_u):
     if not (np.all(np.isfinite(lb)) and np.all(np.isfinite(ub)) and np.all(lb < ub)):
         raise ValueError("F_u must bound every input from both sides (finite, non-empty box)")
     return lb, ub
+
+
+def is_box_Fu(F_u):
+    """True where every row of F_u has exactly one non-zero: the rows of a box, which go through box_from_Fu; a row with two or
+    more makes F_u a polytope, which the solve_poly / rollout_poly calls serve.  (A row of zeros is left to box_from_Fu's error.)"""
+    F_u = np.atleast_2d(np.asarray(F_u, dtype=np.float64))
+    return not np.any(np.count_nonzero(F_u, axis=1) >= 2)
 
 
 def _f64(a, shape=None):
@@ -247,6 +256,53 @@ class BatchSolver:
         if A_true.ndim == 3:
             return _f64(A_true, (nx, nx, Bsz)), _f64(B_true, (nx, nu, Bsz)), 1
         return _f64(A_true, (nx, nx)), _f64(B_true, (nx, nu)), 0
+
+    @staticmethod
+    def _Fu(F_u, nu):
+        F_u = np.ascontiguousarray(np.atleast_2d(np.asarray(F_u, dtype=np.float64)))
+        if F_u.ndim != 2 or F_u.shape[1] != nu:
+            raise ValueError(f"F_u must be (m, {nu}), got {F_u.shape}")
+        return F_u
+
+    def solve_poly_batch(self, N, A, B, Q, R, P, F_u, x0, x_ref=None, u_ref=None, want_plan=False, want_lam=False, max_iter=0):
+        """solve_batch under F_u u_i <= 1 for any (m, nu) matrix F_u (lqmpc_solve_poly_batch; N nu <= 64, m <= 16).
+        want_plan: also "U_plan" (nu, N, Bsz) and "X_plan" (nx, N + 1, Bsz); want_lam: also "lam" (m, N, Bsz), the multipliers of the
+        rows as given.  max_iter caps the active-set passes of a solve (0: 10 N nu + 20); status 1 where it was reached."""
+        A, B, nx, nu, Bsz = self._dims(A, B)
+        Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
+        F_u, x0 = self._Fu(F_u, nu), _f64(x0, (nx, Bsz))
+        m = F_u.shape[0]
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        u0 = np.empty((nu, Bsz)); VN = np.empty(Bsz)
+        status = np.empty(Bsz, dtype=np.int32); iters = np.empty(Bsz, dtype=np.int32)
+        Up = np.empty((nu, N, Bsz)) if want_plan else None
+        Xp = np.empty((nx, N + 1, Bsz)) if want_plan else None
+        lam = np.empty((m, N, Bsz)) if want_lam else None
+        _lib.check(self._L.lqmpc_solve_poly_batch(self._h, nx, nu, N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P), _ptr(F_u), m,
+                                                  _ptr(x0), _ptr(x_ref), _ptr(u_ref), int(max_iter), _ptr(u0), _ptr(VN), _ptr(Up),
+                                                  _ptr(Xp), _ptr(lam), _ptr(status), _ptr(iters)))
+        out = {"u_0": u0, "V_N": VN, "status": status, "iters": iters}
+        if want_plan:
+            out["U_plan"], out["X_plan"] = Up, Xp
+        if want_lam:
+            out["lam"] = lam
+        return out
+
+    def rollout_poly_batch(self, T, N, A, B, Q, R, P, F_u, x0, A_true, B_true, x_ref=None, u_ref=None, want_traj=False, max_iter=0):
+        """rollout_batch under F_u u_i <= 1 for any (m, nu) matrix F_u (lqmpc_rollout_poly_batch): T closed-loop steps, one launch."""
+        A, B, nx, nu, Bsz = self._dims(A, B)
+        Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
+        F_u, x0 = self._Fu(F_u, nu), _f64(x0, (nx, Bsz))
+        A_true, B_true, per_inst = self._plant(A_true, B_true, nx, nu, Bsz)
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        JT = np.empty(Bsz)
+        X = np.empty((nx, T + 1, Bsz)) if want_traj else None
+        U = np.empty((nu, T, Bsz)) if want_traj else None
+        status = np.empty(Bsz, dtype=np.int32); iters = np.empty(Bsz, dtype=np.int32)
+        _lib.check(self._L.lqmpc_rollout_poly_batch(self._h, nx, nu, N, Bsz, T, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P), _ptr(F_u),
+                                                    F_u.shape[0], _ptr(x0), _ptr(A_true), _ptr(B_true), per_inst, _ptr(x_ref),
+                                                    _ptr(u_ref), int(max_iter), _ptr(JT), _ptr(X), _ptr(U), _ptr(status), _ptr(iters)))
+        return {"J_T": JT, "X": X, "U": U, "status": status, "iters": iters}
 
     def rollout_tape_batch(self, T, N, A, B, Q, R, P, lb, ub, x0, A_true, B_true, x_ref=None, u_ref=None):
         """The closed loop of rollout_batch, leaving a tape (lqmpc_rollout_tape_batch): "J_T" (Bsz,), "X" (nx, T + 1, Bsz),
@@ -521,6 +577,28 @@ class BatchSolver:
                                                    _ptr(lb), _ptr(ub), _ptr(dx0), _ptr(A_true), _ptr(B_true),
                                                    1 if true_per_instance else 0, _ptr(x_ref), _ptr(u_ref),
                                                    _ptr(dJT), _ptr(dX), _ptr(dU), _ptr(dstatus), _ptr(diters)))
+
+    def solve_poly_batch_dev(self, nx, nu, N, Bsz, dA, dB, Q, R, P, F_u, dx0, du0, dVN, dUplan=None, dXplan=None, dlam=None, dstatus=None,
+                             diters=None, x_ref=None, u_ref=None, max_iter=0):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_solve_poly_batch_dev).  dlam is
+        (m, N, Bsz)."""
+        Q, R, P, F_u = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), self._Fu(F_u, nu)
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        _lib.check(self._L.lqmpc_solve_poly_batch_dev(self._h, nx, nu, N, Bsz, _ptr(dA), _ptr(dB), _ptr(Q), _ptr(R), _ptr(P), _ptr(F_u),
+                                                      F_u.shape[0], _ptr(dx0), _ptr(x_ref), _ptr(u_ref), int(max_iter), _ptr(du0),
+                                                      _ptr(dVN), _ptr(dUplan), _ptr(dXplan), _ptr(dlam), _ptr(dstatus), _ptr(diters)))
+
+    def rollout_poly_batch_dev(self, nx, nu, N, Bsz, T, dA, dB, Q, R, P, F_u, dx0, A_true, B_true, dJT, dX=None, dU=None, dstatus=None,
+                               diters=None, true_per_instance=False, x_ref=None, u_ref=None, max_iter=0):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once (lqmpc_rollout_poly_batch_dev)."""
+        Q, R, P, F_u = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx)), self._Fu(F_u, nu)
+        if not true_per_instance:
+            A_true, B_true = _f64(A_true, (nx, nx)), _f64(B_true, (nx, nu))
+        x_ref, u_ref = _ref_or_none(x_ref, nx, N), _ref_or_none(u_ref, nu, N)
+        _lib.check(self._L.lqmpc_rollout_poly_batch_dev(self._h, nx, nu, N, Bsz, T, _ptr(dA), _ptr(dB), _ptr(Q), _ptr(R), _ptr(P),
+                                                        _ptr(F_u), F_u.shape[0], _ptr(dx0), _ptr(A_true), _ptr(B_true),
+                                                        1 if true_per_instance else 0, _ptr(x_ref), _ptr(u_ref), int(max_iter),
+                                                        _ptr(dJT), _ptr(dX), _ptr(dU), _ptr(dstatus), _ptr(diters)))
 
     def rollout_tape_batch_dev(self, nx, nu, N, Bsz, T, dA, dB, Q, R, P, lb, ub, dx0, A_true, B_true, dJT, dUtape, dX=None, dU=None,
                                dstatus=None, diters=None, dstatus_tape=None, true_per_instance=False, x_ref=None, u_ref=None):
@@ -863,7 +941,8 @@ def default_solver():
 
 
 class LQ_MPC_Controller:
-    """Open-loop LQ MPC solve; drop-in for utils_class.py:18-91 (box-shaped F_u only)."""
+    """Open-loop LQ MPC solve; drop-in for utils_class.py:18-91.  An F_u whose rows have one non-zero each is a box and runs on the
+    box kernels; a row with two or more makes it a polytope, served by solve_poly_batch (local_law is not: NotImplementedError)."""
 
     def __init__(self, N, A, B, Q, R, P, F_u, solver=None):
         self.N = int(N)
@@ -873,7 +952,8 @@ class LQ_MPC_Controller:
         self.R = np.asarray(R, dtype=np.float64)
         self.P = np.asarray(P, dtype=np.float64)
         self.F_u = np.asarray(F_u, dtype=np.float64)
-        self.lb, self.ub = box_from_Fu(self.F_u)
+        self.poly = not is_box_Fu(self.F_u)
+        self.lb, self.ub = (None, None) if self.poly else box_from_Fu(self.F_u)
         self._solver = solver
         # the decision variable of utils_class.py:46: after solve(), u.value is the (nu, N) optimal plan of that call
         self.u = PlanVariable()
@@ -885,8 +965,12 @@ class LQ_MPC_Controller:
         """Returns {'u_0': (nu,) ndarray, 'V_N': float} as utils_class.py:91."""
         nx = self.A.shape[0]
         x0 = np.asarray(x0, dtype=np.float64).reshape(nx, 1)
-        out = self._s().solve_batch(self.N, self.A[:, :, None], self.B[:, :, None], self.Q, self.R, self.P,
-                                    self.lb, self.ub, x0, x_ref, u_ref, want_plan=True)
+        if self.poly:
+            out = self._s().solve_poly_batch(self.N, self.A[:, :, None], self.B[:, :, None], self.Q, self.R, self.P, self.F_u, x0,
+                                             x_ref, u_ref, want_plan=True)
+        else:
+            out = self._s().solve_batch(self.N, self.A[:, :, None], self.B[:, :, None], self.Q, self.R, self.P,
+                                        self.lb, self.ub, x0, x_ref, u_ref, want_plan=True)
         self.last_status = int(out["status"][0])
         self.u.value = out["U_plan"][:, :, 0].copy()
         return {"u_0": out["u_0"][:, 0].copy(), "V_N": float(out["V_N"][0])}
@@ -894,6 +978,9 @@ class LQ_MPC_Controller:
     def local_law(self, x0, x_ref, u_ref):
         """Additive: the affine law the controller follows around x0, u_0 = K_0 x + k_0 for x in the critical region of x0.
         Returns (K_0, k_0) as (nu, nx) and (nu,) arrays; u.value becomes the plan at x0, as after solve()."""
+        if self.poly:
+            raise NotImplementedError("local_law serves a box-shaped F_u only: the sens calls do not cover a polytope (a row of F_u "
+                                      "with two or more non-zeros)")
         nx = self.A.shape[0]
         x0 = np.asarray(x0, dtype=np.float64).reshape(nx, 1)
         out = self._s().solve_batch(self.N, self.A[:, :, None], self.B[:, :, None], self.Q, self.R, self.P,
@@ -909,7 +996,10 @@ class LQ_MPC_Controller:
         K = x0s.shape[1]
         A = np.repeat(self.A[:, :, None], K, 2)
         B = np.repeat(self.B[:, :, None], K, 2)
-        out = self._s().solve_batch(self.N, A, B, self.Q, self.R, self.P, self.lb, self.ub, x0s, x_ref, u_ref, want_plan=True)
+        if self.poly:
+            out = self._s().solve_poly_batch(self.N, A, B, self.Q, self.R, self.P, self.F_u, x0s, x_ref, u_ref, want_plan=True)
+        else:
+            out = self._s().solve_batch(self.N, A, B, self.Q, self.R, self.P, self.lb, self.ub, x0s, x_ref, u_ref, want_plan=True)
         self.u.value = out["U_plan"]
         return {"u_0": out["u_0"], "V_N": out["V_N"], "status": out["status"]}
 
@@ -926,7 +1016,8 @@ class LQ_MPC_Simulator:
         self.R = np.asarray(R, dtype=np.float64)
         self.P = np.asarray(P, dtype=np.float64)
         self.F_u = np.asarray(F_u, dtype=np.float64)
-        self.lb, self.ub = box_from_Fu(self.F_u)
+        self.poly = not is_box_Fu(self.F_u)          # a row with two or more non-zeros: rollout_poly_batch
+        self.lb, self.ub = (None, None) if self.poly else box_from_Fu(self.F_u)
         self.U = np.zeros((self.B.shape[1], self.T))
         self.X = np.zeros((self.A.shape[1], self.T + 1))
         self._solver = solver
@@ -936,9 +1027,14 @@ class LQ_MPC_Simulator:
         s = self._solver if self._solver is not None else default_solver()
         nx = self.A.shape[0]
         x0 = np.asarray(x0, dtype=np.float64).reshape(nx, 1)
-        out = s.rollout_batch(self.T, self.N, self.A[:, :, None], self.B[:, :, None], self.Q, self.R, self.P,
-                              self.lb, self.ub, x0, np.asarray(A_true, dtype=np.float64),
-                              np.asarray(B_true, dtype=np.float64), x_ref, u_ref, want_traj=True)
+        if self.poly:
+            out = s.rollout_poly_batch(self.T, self.N, self.A[:, :, None], self.B[:, :, None], self.Q, self.R, self.P, self.F_u, x0,
+                                       np.asarray(A_true, dtype=np.float64), np.asarray(B_true, dtype=np.float64), x_ref, u_ref,
+                                       want_traj=True)
+        else:
+            out = s.rollout_batch(self.T, self.N, self.A[:, :, None], self.B[:, :, None], self.Q, self.R, self.P,
+                                  self.lb, self.ub, x0, np.asarray(A_true, dtype=np.float64),
+                                  np.asarray(B_true, dtype=np.float64), x_ref, u_ref, want_traj=True)
         self.X = out["X"][:, :, 0].copy()
         self.U = out["U"][:, :, 0].copy()
         self.last_status = int(out["status"][0])
