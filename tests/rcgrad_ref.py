@@ -80,9 +80,11 @@ def reference(p, kw, At, Bt, X, U_tape, gJT, gX, gU):
     return out
 
 
-def adjoint(N, A, B, Q, R, P, At, Bt, side, X, U_tape, gJT, gX, gU, x_ref=None, u_ref=None, dtype=np.float64, chol=False):
+def adjoint(N, A, B, Q, R, P, At, Bt, side, X, U_tape, gJT, gX, gU, x_ref=None, u_ref=None, dtype=np.float64, chol=False,
+            stats=None):
     """numpy, the algebra of lqmpc_rollout_cost_grad_kernel: side (T, nu, N, Bsz) the faces (-1 lower, +1 upper, 0 free), X
-    (nx, T + 1, Bsz), U_tape (T, nu, N, Bsz).  Returns the seven outputs of KEYS and 'w' (T, nu, Bsz)."""
+    (nx, T + 1, Bsz), U_tape (T, nu, N, Bsz).  Returns the seven outputs of KEYS and 'w' (T, nu, Bsz).  dtype, chol, stats: see
+    sens_ref.stage_solver."""
     cast = lambda a: np.asarray(a, dtype=dtype)
     T, nu, _, Bsz = U_tape.shape
     nx = X.shape[0]
@@ -105,8 +107,8 @@ def adjoint(N, A, B, Q, R, P, At, Bt, side, X, U_tape, gJT, gX, gU, x_ref=None, 
         Xp[:, 0] = Xc[:, t]
         for i in range(N):
             Xp[:, i + 1] = np.einsum("acb,cb->ab", Ac, Xp[:, i]) + np.einsum("akb,kb->ab", Bc, Up[:, i])
-        c = cg.adjoint(N, A, B, Q, R, P, side[t], Xp, Up, w, zero, x_ref, u_ref, dtype=dtype, chol=chol)
-        m = gr.adjoint(N, A, B, Q, R, P, side[t] == 0, Xp, Up, w, zero, x_ref, dtype=dtype, chol=chol)
+        c = cg.adjoint(N, A, B, Q, R, P, side[t], Xp, Up, w, zero, x_ref, u_ref, dtype=dtype, chol=chol, stats=stats)
+        m = gr.adjoint(N, A, B, Q, R, P, side[t] == 0, Xp, Up, w, zero, x_ref, dtype=dtype, chol=chol, stats=stats)
         for k in NAMES:
             out[k] = out[k] + c[k]
         out["g_Q"] = out["g_Q"] + _direct(gam, Xc[:, t])

@@ -150,9 +150,9 @@ def reference(p, kw, At, Bt, X, U_tape, gJT, gX, gU):
     return dict(g_A=gA, g_B=gB, g_x0=lam, g_A_true=gAt, g_B_true=gBt, free=free, ok=ok)
 
 
-def adjoint(N, A, B, Q, R, P, At, Bt, free, X, U_tape, gJT, gX, gU, x_ref=None, dtype=np.float64, chol=False):
+def adjoint(N, A, B, Q, R, P, At, Bt, free, X, U_tape, gJT, gX, gU, x_ref=None, dtype=np.float64, chol=False, stats=None):
     """numpy, the algebra of lqmpc_rollout_grad_kernel: free (T, nu, N, Bsz) the faces, X (nx, T + 1, Bsz), U_tape (T, nu, N, Bsz).
-    Returns {'g_A', 'g_B', 'g_x0', 'g_A_true', 'g_B_true'}."""
+    Returns {'g_A', 'g_B', 'g_x0', 'g_A_true', 'g_B_true'}.  dtype, chol, stats: see sens_ref.stage_solver."""
     cast = lambda a: np.asarray(a, dtype=dtype)
     T, nu, _, Bsz = U_tape.shape
     nx = X.shape[0]
@@ -173,7 +173,7 @@ def adjoint(N, A, B, Q, R, P, At, Bt, free, X, U_tape, gJT, gX, gU, x_ref=None, 
         Xp[:, 0] = Xc[:, t]
         for i in range(N):
             Xp[:, i + 1] = np.einsum("acb,cb->ab", Ac, Xp[:, i]) + np.einsum("akb,kb->ab", Bc, Up[:, i])
-        g = gr.adjoint(N, A, B, Q, R, P, free[t], Xp, Up, w, zero, x_ref, dtype=dtype, chol=chol)
+        g = gr.adjoint(N, A, B, Q, R, P, free[t], Xp, Up, w, zero, x_ref, dtype=dtype, chol=chol, stats=stats)
         gA, gB = gA + g["g_A"], gB + g["g_B"]
         gAt, gBt = gAt + lam[:, None, :] * Xc[:, t][None, :, :], gBt + lam[:, None, :] * u[None, :, :]
         lam = gXc[:, t] + 2 * gam * (Qc @ Xc[:, t]) + np.einsum("bij,ib->jb", Atb, lam) + g["g_x0"]
