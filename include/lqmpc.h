@@ -561,7 +561,7 @@ int lqmpc_rollout_cost_grad_batch_dev(lqmpc_handle *h, int nx, int nu, int N, in
  * pristine factor at every step that follows a step with an add, so rounding does not accumulate over T), x_{t+1} = A_true x_t +
  * B_true u_t, J_T = x_0'Q x_0 + sum_t (x_{t+1}'Q x_{t+1} + u_t'R u_t) summed in that order; X (nx, T+1, Bsz) and U (nu, T, Bsz) may be
  * NULL; status = the largest over the steps, iters = the sum; T in [1, 100000]; A_true / B_true shared (host) or per instance.
- * NOT HERE: the prepared controller, the sens / grad / tape calls, sweep, max_vn and the bound coefficients for a polytope; n > 64; a
+ * NOT HERE (the prepared controller is lqmpc_poly_controller_* below): the sens / grad / tape calls, sweep, max_vn and the bound coefficients for a polytope; n > 64; a
  * per-instance Fu; state constraints; warm start across rollout steps. */
 int lqmpc_solve_poly_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
                            const double *A, const double *B,
@@ -591,6 +591,82 @@ int lqmpc_rollout_poly_batch_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t
                                  const double *A_true, const double *B_true, int true_per_instance,
                                  const double *x_ref, const double *u_ref, int max_iter,
                                  double *dJT, double *dX, double *dU, int32_t *dstatus, int32_t *diters);
+
+/* ---- prepared controller for the polytope problem: factor once, then one polytope QP per instance and measured state ----
+ * For a closed loop the caller owns (a torch plant, recorded data, hardware) whose input set is not a box: create runs the
+ * per-instance set-up of lqmpc_solve_poly_batch once -- W_k = A^k B, the Riccati sums, G = 2H, its Cholesky factor, L^-1 -- and keeps
+ * it in HBM; every step solves the QP at the states it is given from that, in ONE launch (lqmpc_poly_ctl_step_kernel), with no
+ * host-to-device copy and no allocation.  None of the set-up depends on the state; only the linear term does.
+ * A type of its own: the sens and grad calls of lqmpc_controller do not exist for a polytope.
+ * CONTRACT: arguments, layouts, outputs, status and accuracy are those of lqmpc_solve_poly_batch / lqmpc_rollout_poly_batch above.
+ * A, B as there (host; _dev: device), Q, R, P, Fu (m x nu), x_ref, u_ref HOST and copied by create; max_iter is fixed at create
+ * (0 = 10 n + 20) and eps is the handle's option at create -- later lqmpc_set_options do not reach the controller.  The controller
+ * keeps its OWN device copy of the shared block (Q, R, P, Fu, the references): the one-shot calls overwrite the handle's, so one-shot
+ * calls and steps of several controllers may be mixed freely on one handle.  create waits for the stream: A and B are the caller's
+ * again when it returns.
+ * DOMAIN and refusals: those of lqmpc_solve_poly_batch, decided from the arguments before the handle is dereferenced or anything is
+ * enqueued: N nu > 64, m > 16 or an LDS image over 160 KiB gives LQMPC_ERR_UNSUPPORTED with the domain in the message; m < 1, a
+ * NULL Fu, a zero or non-finite row of Fu, max_iter < 0, a NULL handle, A, B, Q, R, P or out, Bsz < 1 give LQMPC_ERR_BAD_ARG.  step,
+ * rollout and set_model refuse a NULL controller, a NULL required array (x, u0; x0, A_true, B_true, JT; A, B) and T outside
+ * [1, 100000] with LQMPC_ERR_BAD_ARG before the controller is dereferenced.
+ * LAYOUT: one record per instance, contiguous, [A (nx nx) | B (nx nu) | W_k, k < N (N nx nu) | Jp (n (n + 1) / 2)], Jp = L^-1 packed by
+ * rows; the stride is rounded up to a multiple of 16 doubles, so records start on 128-byte lines and a wavefront reads its record
+ * with consecutive lanes on consecutive addresses.  lqmpc_poly_controller_record_bytes(nx, nu, N) = 8 x stride is pure host
+ * arithmetic (no handle): 2 560 bytes at (4,2,10), 27 008 at (16,1,64); a negative lqmpc_error outside nx <= 16, nu <= 8, N <= 64,
+ * N nu <= 64.  bytes: the HBM the controller holds, Bsz records and the shared block.  The record's A and B are the controller's
+ * copies of the models: it keeps no others.
+ * BIT FOR BIT: every solve of the polytope kernels starts cold, from the pristine J = L^-T and an empty active set, and the step
+ * runs the statements of the one-shot kernel on the record's values, which are the one-shot set-up's.  So step at x returns the
+ * bits lqmpc_solve_poly_batch returns at x0 = x for the controller's models, weights, Fu and current references -- u0, VN, Uplan,
+ * Xplan, lam, status, iters, and leaving an optional output out leaves the others bit for bit (here VN is optional too, as at
+ * lqmpc_controller_step: the controller owns a buffer for it) -- and rollout returns the bits of
+ * lqmpc_rollout_poly_batch.  A step leaves nothing behind: the records are read-only to step and rollout, so a step does not depend
+ * on the steps or rollouts before it.
+ * set_reference: new references for every later step and rollout, HOST, NULL = zeros.  No part of a record depends on the
+ * references, so NO kernel runs: the two reference blocks of the controller's shared copy are rewritten by one copy on the handle's
+ * stream, behind every step enqueued so far and in front of every later one.  The arrays are copied before the call returns.
+ * set_model: new models for `count` instances, laid out and checked as lqmpc_controller_set_model states (instance-minor over the
+ * update; idx == NULL needs count == Bsz; count == 0 does nothing; the host flavour checks idx for range and duplicates before
+ * anything is enqueued and waits for the stream, the device flavour returns at once and its kernel skips an entry outside [0, Bsz)
+ * whole, so a bad index never writes).  One launch of lqmpc_poly_ctl_factor_kernel over the update, workgroup j writing record
+ * idx[j]; an unlisted record keeps every bit.
+ * rollout: T closed-loop steps from the records in one launch (lqmpc_poly_ctl_rollout_kernel), read-only on the controller.  A
+ * shared plant is a HOST pointer in both flavours, staged per call in memory the controller owns; a per-instance plant is a host
+ * pointer in the host flavour and a device pointer in _dev.
+ * Non-finite data: a non-finite model (at create or set_model) or state gives status 2 at that instance's steps and leaves the
+ * other instances and the controller untouched.  kernel: "lqmpc_poly_ctl_step_kernel"; step, rollout and set_model set the
+ * handle's lqmpc_last_kernel.  destroy: NULL is fine.
+ * NOT HERE: warm start across steps (the dual method needs a dual-feasible start, and the cold start is what the bit-for-bit
+ * equality rests on); the sens / grad / tape calls, MPCLayer, sweep, max_vn and the bound coefficients for a polytope; n > 64; a
+ * per-instance Fu; state constraints. */
+typedef struct lqmpc_poly_controller lqmpc_poly_controller;
+int lqmpc_poly_controller_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                                 const double *A, const double *B,
+                                 const double *Q, const double *R, const double *P,
+                                 const double *Fu, int m,
+                                 const double *x_ref, const double *u_ref, int max_iter, lqmpc_poly_controller **out);
+int lqmpc_poly_controller_create_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz,
+                                     const double *dA, const double *dB,
+                                     const double *Q, const double *R, const double *P,
+                                     const double *Fu, int m,
+                                     const double *x_ref, const double *u_ref, int max_iter, lqmpc_poly_controller **out);
+int lqmpc_poly_controller_step(lqmpc_poly_controller *c, const double *x, double *u0, double *VN, double *Uplan, double *Xplan,
+                               double *lam, int32_t *status, int32_t *iters);
+int lqmpc_poly_controller_step_dev(lqmpc_poly_controller *c, const double *dx, double *du0, double *dVN, double *dUplan, double *dXplan,
+                                   double *dlam, int32_t *dstatus, int32_t *diters);
+int lqmpc_poly_controller_rollout(lqmpc_poly_controller *c, int T, const double *x0,
+                                  const double *A_true, const double *B_true, int true_per_instance,
+                                  double *JT, double *X, double *U, int32_t *status, int32_t *iters);
+int lqmpc_poly_controller_rollout_dev(lqmpc_poly_controller *c, int T, const double *dx0,
+                                      const double *A_true, const double *B_true, int true_per_instance,
+                                      double *dJT, double *dX, double *dU, int32_t *dstatus, int32_t *diters);
+int lqmpc_poly_controller_set_reference(lqmpc_poly_controller *c, const double *x_ref, const double *u_ref);
+int lqmpc_poly_controller_set_model(lqmpc_poly_controller *c, int64_t count, const int32_t *idx, const double *A, const double *B);
+int lqmpc_poly_controller_set_model_dev(lqmpc_poly_controller *c, int64_t count, const int32_t *didx, const double *dA, const double *dB);
+int64_t lqmpc_poly_controller_record_bytes(int nx, int nu, int N);
+int64_t lqmpc_poly_controller_bytes(const lqmpc_poly_controller *c);
+const char *lqmpc_poly_controller_kernel(const lqmpc_poly_controller *c);
+int lqmpc_poly_controller_destroy(lqmpc_poly_controller *c);
 
 /* ---- M_V = max_k V_N(x0s[:,k]) per instance (utils_class.py:816-824, 899-907) ---- */
 int lqmpc_max_vn_batch(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, int K,

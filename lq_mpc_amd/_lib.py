@@ -44,6 +44,10 @@ EXPORTS = [
     "lqmpc_rollout_tape_batch", "lqmpc_rollout_tape_batch_dev", "lqmpc_rollout_grad_batch", "lqmpc_rollout_grad_batch_dev",
     "lqmpc_rollout_cost_grad_batch", "lqmpc_rollout_cost_grad_batch_dev",
     "lqmpc_solve_poly_batch", "lqmpc_solve_poly_batch_dev", "lqmpc_rollout_poly_batch", "lqmpc_rollout_poly_batch_dev",
+    "lqmpc_poly_controller_create", "lqmpc_poly_controller_create_dev", "lqmpc_poly_controller_step", "lqmpc_poly_controller_step_dev",
+    "lqmpc_poly_controller_rollout", "lqmpc_poly_controller_rollout_dev", "lqmpc_poly_controller_set_reference",
+    "lqmpc_poly_controller_set_model", "lqmpc_poly_controller_set_model_dev", "lqmpc_poly_controller_record_bytes",
+    "lqmpc_poly_controller_bytes", "lqmpc_poly_controller_kernel", "lqmpc_poly_controller_destroy",
 ]
 
 
@@ -174,6 +178,23 @@ def lib():
     L.lqmpc_controller_kernel.argtypes = [_H]
     L.lqmpc_controller_kernel.restype = ctypes.c_char_p
     L.lqmpc_controller_destroy.argtypes = [_H]
+    pctl_create_args = dims + [P] * 6 + [ctypes.c_int] + [P] * 2 + [ctypes.c_int, ctypes.POINTER(_H)]
+    L.lqmpc_poly_controller_create.argtypes = pctl_create_args
+    L.lqmpc_poly_controller_create_dev.argtypes = pctl_create_args
+    L.lqmpc_poly_controller_step.argtypes = [_H] + [P] * 8
+    L.lqmpc_poly_controller_step_dev.argtypes = [_H] + [P] * 8
+    L.lqmpc_poly_controller_rollout.argtypes = ctl_roll_args
+    L.lqmpc_poly_controller_rollout_dev.argtypes = ctl_roll_args
+    L.lqmpc_poly_controller_set_reference.argtypes = [_H, P, P]
+    L.lqmpc_poly_controller_set_model.argtypes = [_H, ctypes.c_int64, P, P, P]
+    L.lqmpc_poly_controller_set_model_dev.argtypes = [_H, ctypes.c_int64, P, P, P]
+    L.lqmpc_poly_controller_record_bytes.argtypes = [ctypes.c_int] * 3
+    L.lqmpc_poly_controller_record_bytes.restype = ctypes.c_int64
+    L.lqmpc_poly_controller_bytes.argtypes = [_H]
+    L.lqmpc_poly_controller_bytes.restype = ctypes.c_int64
+    L.lqmpc_poly_controller_kernel.argtypes = [_H]
+    L.lqmpc_poly_controller_kernel.restype = ctypes.c_char_p
+    L.lqmpc_poly_controller_destroy.argtypes = [_H]
     # code objects of run-time compiled shapes are kept next to the library (falls back to memory only if not writable)
     L.lqmpc_jit_cache_dir(JIT_CACHE.encode())
     _lib = L

@@ -2416,3 +2416,308 @@ int lqmpc_controller_destroy(lqmpc_controller *c)
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Prepared controller for polytopic input constraints (kernels: lqmpc_poly.hip, launch_poly_ctl): one record [A | B | W | Jp] per
+// instance in HBM, and the controller's own device copy of the shared block -- the one-shot calls overwrite the handle's.
+struct lqmpc_poly_controller {
+    lqmpc_handle *h = nullptr;
+    uint64_t id = 0;                          // what the handle remembers of the controller that set last_kernel
+    double eps = 0.0;                         // the handle's option when the controller was made
+    int nx = 0, nu = 0, N = 0, m = 0, max_iter = 0;
+    int64_t Bsz = 0;
+    lqmpc::PolyOff so{};
+    std::vector<double> sh_host;              // [Q | R | P | Fu | xref | uref | At | Bt]: what the device copy holds or is about to
+    void *sh = nullptr, *rec = nullptr;
+    void *vn = nullptr;                       // V_N of a step whose caller passed NULL (the kernel always writes it)
+    long long rstride = 0;
+    size_t bytes = 0;
+    HostBuf pin[2];                           // pinned sources of the block's uploads, taken in turn (as the handle's shared_pin)
+    int turn = 0;
+};
+
+namespace {
+
+void pctl_free(lqmpc_poly_controller *c)
+{
+    for (void *q : {c->sh, c->rec, c->vn}) if (q) (void)hipFree(q);
+    for (HostBuf &hb : c->pin) {
+        if (hb.p) (void)hipHostFree(hb.p);
+        if (hb.ev) (void)hipEventDestroy(hb.ev);
+    }
+    delete c;
+}
+
+int pctl_alloc(lqmpc_poly_controller *c, void **q, size_t bytes)
+{
+    const hipError_t e = hipMalloc(q, bytes);
+    if (e != hipSuccess) { *q = nullptr; return fail(LQMPC_ERR_ALLOC, std::string("hipMalloc (polytope controller): ") + hipGetErrorString(e)); }
+    c->bytes += bytes;
+    return 0;
+}
+
+// doubles [off, off + count) of sh_host on their way to the device copy, ordered on the stream; no allocation after create
+int pctl_upload(lqmpc_poly_controller *c, size_t off, size_t count)
+{
+    const size_t bytes = count * sizeof(double);
+    HostBuf &hb = c->pin[c->turn ^= 1];
+    const int rc = ensure_host(hb, c->sh_host.size() * sizeof(double));
+    if (rc) return rc;
+    if (hb.ev_valid) HIP_TRY(hipEventSynchronize(hb.ev));
+    memcpy(hb.p, c->sh_host.data() + off, bytes);
+    HIP_TRY(hipMemcpyAsync((double *)c->sh + off, hb.p, bytes, hipMemcpyHostToDevice, c->h->stream));
+    HIP_TRY(hipEventRecord(hb.ev, c->h->stream));
+    hb.ev_valid = true;
+    return 0;
+}
+
+lqmpc::PolyParams pctl_params(const lqmpc_poly_controller *c)
+{
+    lqmpc::PolyParams p{};
+    p.nx = c->nx; p.nu = c->nu; p.N = c->N; p.m = c->m; p.T = 0; p.max_iter = c->max_iter; p.eps = c->eps; p.Bsz = c->Bsz;
+    p.sh = (const double *)c->sh; p.so = c->so;
+    p.rec = (double *)c->rec; p.rstride = c->rstride; p.nrec = c->Bsz; p.idx = nullptr;
+    return p;
+}
+
+int pctl_launch(lqmpc_poly_controller *c, const lqmpc::PolyParams &p, int what)
+{
+    const char *name = nullptr;
+    if (!lqmpc::launch_poly_ctl(p, what, c->h->stream, &name)) return fail(LQMPC_ERR_HIP, "the polytope controller kernel's launch failed");
+    HIP_TRY(hipGetLastError());
+    set_last_kernel(c->h, name, c->id);
+    return 0;
+}
+
+// the factor launch over an update of `count` models (device, instance-minor over count), its records redirected through didx
+int pctl_factor(lqmpc_poly_controller *c, int64_t count, const int32_t *didx, const double *dA, const double *dB)
+{
+    lqmpc::PolyParams p = pctl_params(c);
+    p.Bsz = count; p.A = dA; p.B = dB; p.idx = didx;
+    return pctl_launch(c, p, lqmpc::POLY_CTL_FACTOR);
+}
+
+int pctl_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B, bool on_device, const double *Q,
+                const double *R, const double *P, const double *Fu, int m, const double *x_ref, const double *u_ref, int max_iter,
+                lqmpc_poly_controller **out)
+{
+    if (out) *out = nullptr;
+    int rc = poly_check(h, nx, nu, N, Bsz, 0, false, A, B, Q, R, P, Fu, m, A, nullptr, nullptr, max_iter, out, out);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    lqmpc_poly_controller *c = new lqmpc_poly_controller();
+    c->h = h; c->id = ++h->ctl_ids; c->eps = h->opt.eps; c->nx = nx; c->nu = nu; c->N = N; c->m = m; c->max_iter = max_iter; c->Bsz = Bsz;
+    c->rstride = lqmpc::poly_rec_layout(nx, nu, N).stride;
+    std::vector<double> &sh = c->sh_host;
+    auto put = [&](const double *src, int count) {
+        int off = (int)sh.size();
+        sh.resize(sh.size() + count, 0.0);
+        if (src) memcpy(sh.data() + off, src, sizeof(double) * count);
+        return off;
+    };
+    c->so.Q = put(Q, nx * nx);
+    c->so.R = put(R, nu * nu);
+    c->so.P = put(P, nx * nx);
+    c->so.Fu = put(Fu, m * nu);
+    c->so.xref = put(x_ref, nx * N);
+    c->so.uref = put(u_ref, nu * N);
+    c->so.At = put(nullptr, nx * nx);
+    c->so.Bt = put(nullptr, nx * nu);
+    const size_t rec_bytes = (size_t)Bsz * (size_t)c->rstride * sizeof(double);
+    rc = pctl_alloc(c, &c->sh, sh.size() * sizeof(double));
+    if (!rc) rc = pctl_alloc(c, &c->rec, rec_bytes);
+    if (!rc) rc = pctl_alloc(c, &c->vn, (size_t)Bsz * sizeof(double));
+    for (HostBuf &hb : c->pin) if (!rc) rc = ensure_host(hb, sh.size() * sizeof(double));
+    if (!rc) rc = pctl_upload(c, 0, sh.size());
+    if (rc) { pctl_free(c); return rc; }
+    // (the padding behind a record is never read; zeroed so that the controller's memory is defined everywhere)
+    hipError_t e = hipMemsetAsync(c->rec, 0, rec_bytes, h->stream);
+    if (e != hipSuccess) { pctl_free(c); return fail(LQMPC_ERR_HIP, std::string("polytope controller set-up: ") + hipGetErrorString(e)); }
+    if (on_device) rc = pctl_factor(c, Bsz, nullptr, A, B);
+    else {
+        Stager s{h};
+        const double *dA, *dB;
+        s.in(A, (size_t)Bsz * nx * nx, dA); s.in(B, (size_t)Bsz * nx * nu, dB);
+        rc = s.upload();
+        if (!rc) rc = pctl_factor(c, Bsz, nullptr, dA, dB);
+    }
+    // the caller may overwrite A and B as soon as this returns
+    if (!rc) {
+        e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(LQMPC_ERR_HIP, std::string("polytope controller set-up: ") + hipGetErrorString(e));
+    }
+    if (rc) { pctl_free(c); return rc; }
+    *out = c;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t lqmpc_poly_controller_record_bytes(int nx, int nu, int N)
+{
+    const int rc = check_dims(nx, nu, N, 1);
+    if (rc) return rc;
+    if (N * nu > POLY_MAX_NVAR) return fail(LQMPC_ERR_UNSUPPORTED, "the polytope kernels serve N*nu<=64");
+    return (int64_t)sizeof(double) * lqmpc::poly_rec_layout(nx, nu, N).stride;
+}
+
+int lqmpc_poly_controller_create(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *A, const double *B, const double *Q,
+                                 const double *R, const double *P, const double *Fu, int m, const double *x_ref, const double *u_ref,
+                                 int max_iter, lqmpc_poly_controller **out)
+{
+    return pctl_create(h, nx, nu, N, Bsz, A, B, false, Q, R, P, Fu, m, x_ref, u_ref, max_iter, out);
+}
+
+int lqmpc_poly_controller_create_dev(lqmpc_handle *h, int nx, int nu, int N, int64_t Bsz, const double *dA, const double *dB,
+                                     const double *Q, const double *R, const double *P, const double *Fu, int m, const double *x_ref,
+                                     const double *u_ref, int max_iter, lqmpc_poly_controller **out)
+{
+    return pctl_create(h, nx, nu, N, Bsz, dA, dB, true, Q, R, P, Fu, m, x_ref, u_ref, max_iter, out);
+}
+
+int lqmpc_poly_controller_step_dev(lqmpc_poly_controller *c, const double *dx, double *du0, double *dVN, double *dUplan, double *dXplan,
+                                   double *dlam, int32_t *dstatus, int32_t *diters)
+{
+    if (!c || !dx || !du0) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    HIP_TRY(hipSetDevice(c->h->device));
+    lqmpc::PolyParams p = pctl_params(c);
+    p.x0 = dx;
+    p.u0 = du0; p.VN = dVN ? dVN : (double *)c->vn; p.Uplan = dUplan; p.Xplan = dXplan; p.lam = dlam; p.status = dstatus; p.iters = diters;
+    return pctl_launch(c, p, lqmpc::POLY_CTL_STEP);
+}
+
+int lqmpc_poly_controller_step(lqmpc_poly_controller *c, const double *x, double *u0, double *VN, double *Uplan, double *Xplan, double *lam,
+                               int32_t *status, int32_t *iters)
+{
+    if (!c || !x || !u0) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)c->Bsz, nx = (size_t)c->nx, nu = (size_t)c->nu, N = (size_t)c->N;
+    const double *dx;
+    double *du0, *dVN, *dUp, *dXp, *dlam;
+    int32_t *dst, *dit;
+    s.in(x, b * nx, dx);
+    s.out(u0, b * nu, du0); s.out(VN, b, dVN); s.out(Uplan, b * nu * N, dUp); s.out(Xplan, b * nx * (N + 1), dXp);
+    s.out(lam, b * (size_t)c->m * N, dlam); s.out(status, b, dst); s.out(iters, b, dit);
+    int rc = s.upload();
+    if (!rc) rc = lqmpc_poly_controller_step_dev(c, dx, du0, dVN, dUp, dXp, dlam, dst, dit);
+    return rc ? rc : s.finish();
+}
+
+// T closed-loop steps of every instance from the records, in one launch; read-only on the records.  A shared plant is a host pointer
+// in both flavours: staged in the controller's own shared block.
+int lqmpc_poly_controller_rollout_dev(lqmpc_poly_controller *c, int T, const double *dx0, const double *A_true, const double *B_true,
+                                      int true_per_instance, double *dJT, double *dX, double *dU, int32_t *dstatus, int32_t *diters)
+{
+    if (!c || !dx0 || !A_true || !B_true || !dJT) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (T < 1 || T > 100000) return fail(LQMPC_ERR_BAD_ARG, "T must be in [1,100000]");
+    HIP_TRY(hipSetDevice(c->h->device));
+    lqmpc::PolyParams p = pctl_params(c);
+    p.T = T; p.x0 = dx0;
+    p.JT = dJT; p.X = dX; p.U = dU; p.status = dstatus; p.iters = diters;
+    if (true_per_instance) { p.At = A_true; p.Bt = B_true; p.sE = c->Bsz; p.sI = 1; }
+    else {
+        const int nx = c->nx, nu = c->nu;
+        memcpy(c->sh_host.data() + c->so.At, A_true, sizeof(double) * nx * nx);
+        memcpy(c->sh_host.data() + c->so.Bt, B_true, sizeof(double) * nx * nu);
+        const int rc = pctl_upload(c, (size_t)c->so.At, (size_t)(nx * nx + nx * nu));      // (At and Bt are neighbours in the block)
+        if (rc) return rc;
+        p.At = p.sh + c->so.At; p.Bt = p.sh + c->so.Bt; p.sE = 1; p.sI = 0;
+    }
+    return pctl_launch(c, p, lqmpc::POLY_CTL_ROLLOUT);
+}
+
+int lqmpc_poly_controller_rollout(lqmpc_poly_controller *c, int T, const double *x0, const double *A_true, const double *B_true,
+                                  int true_per_instance, double *JT, double *X, double *U, int32_t *status, int32_t *iters)
+{
+    if (!c || !x0 || !A_true || !B_true || !JT) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (T < 1 || T > 100000) return fail(LQMPC_ERR_BAD_ARG, "T must be in [1,100000]");
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t b = (size_t)c->Bsz, nx = (size_t)c->nx, nu = (size_t)c->nu;
+    const double *dx0, *dAt = A_true, *dBt = B_true;
+    double *dJT, *dX, *dU;
+    int32_t *dst, *dit;
+    s.in(x0, b * nx, dx0);
+    if (true_per_instance) { s.in(A_true, b * nx * nx, dAt); s.in(B_true, b * nx * nu, dBt); }
+    s.out(JT, b, dJT); s.out(X, b * nx * (size_t)(T + 1), dX); s.out(U, b * nu * (size_t)T, dU); s.out(status, b, dst); s.out(iters, b, dit);
+    int rc = s.upload();
+    if (!rc) rc = lqmpc_poly_controller_rollout_dev(c, T, dx0, dAt, dBt, true_per_instance, dJT, dX, dU, dst, dit);
+    return rc ? rc : s.finish();
+}
+
+// No part of a record depends on the references: the two reference blocks of the controller's shared copy are rewritten, behind
+// every step enqueued so far and in front of every later one.  No kernel.
+int lqmpc_poly_controller_set_reference(lqmpc_poly_controller *c, const double *x_ref, const double *u_ref)
+{
+    if (!c) return fail(LQMPC_ERR_BAD_ARG, "controller is NULL");
+    HIP_TRY(hipSetDevice(c->h->device));
+    const size_t nxr = (size_t)c->nx * c->N, nur = (size_t)c->nu * c->N;
+    double *xr = c->sh_host.data() + c->so.xref, *ur = c->sh_host.data() + c->so.uref;
+    if (x_ref) memcpy(xr, x_ref, sizeof(double) * nxr); else std::fill(xr, xr + nxr, 0.0);
+    if (u_ref) memcpy(ur, u_ref, sizeof(double) * nur); else std::fill(ur, ur + nur, 0.0);
+    return pctl_upload(c, (size_t)c->so.xref, nxr + nur);                                   // (xref and uref are neighbours in the block)
+}
+
+// New models for `count` instances: the factor launch of create over the update, its records redirected through didx.  The records
+// hold the controller's copies of A and B, so the launch refreshes those too; a record that is not listed is not touched.
+int lqmpc_poly_controller_set_model_dev(lqmpc_poly_controller *c, int64_t count, const int32_t *didx, const double *dA, const double *dB)
+{
+    if (!c) return fail(LQMPC_ERR_BAD_ARG, "controller is NULL");
+    if (count == 0) return 0;
+    if (!dA || !dB) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (count < 0 || count > c->Bsz) return fail(LQMPC_ERR_BAD_ARG, "count must be in [0, Bsz]");
+    if (!didx && count != c->Bsz) return fail(LQMPC_ERR_BAD_ARG, "idx == NULL replaces every model: count must equal Bsz");
+    HIP_TRY(hipSetDevice(c->h->device));
+    return pctl_factor(c, count, didx, dA, dB);
+}
+
+int lqmpc_poly_controller_set_model(lqmpc_poly_controller *c, int64_t count, const int32_t *idx, const double *A, const double *B)
+{
+    if (!c) return fail(LQMPC_ERR_BAD_ARG, "controller is NULL");
+    if (count == 0) return 0;
+    if (!A || !B) return fail(LQMPC_ERR_BAD_ARG, "NULL argument");
+    if (count < 0 || count > c->Bsz) return fail(LQMPC_ERR_BAD_ARG, "count must be in [0, Bsz]");
+    if (!idx && count != c->Bsz) return fail(LQMPC_ERR_BAD_ARG, "idx == NULL replaces every model: count must equal Bsz");
+    if (idx) {
+        // distinct and in range, before anything is enqueued
+        std::vector<char> seen((size_t)c->Bsz, 0);
+        for (int64_t j = 0; j < count; ++j) {
+            if (idx[j] < 0 || idx[j] >= c->Bsz) return fail(LQMPC_ERR_BAD_ARG, "idx holds an instance outside [0, Bsz)");
+            if (seen[(size_t)idx[j]]) return fail(LQMPC_ERR_BAD_ARG, "idx holds an instance twice");
+            seen[(size_t)idx[j]] = 1;
+        }
+    }
+    lqmpc_handle *h = c->h;
+    HIP_TRY(hipSetDevice(h->device));
+    Stager s{h};
+    const size_t k = (size_t)count, nx = (size_t)c->nx, nu = (size_t)c->nu;
+    const int32_t *didx;
+    const double *dA, *dB;
+    s.in(idx, k, didx); s.in(A, k * nx * nx, dA); s.in(B, k * nx * nu, dB);
+    int rc = s.upload();
+    if (!rc) rc = lqmpc_poly_controller_set_model_dev(c, count, didx, dA, dB);
+    if (rc) return rc;
+    // the staging is the handle's and the caller may overwrite A, B and idx as soon as this returns: wait, as create does
+    return s.finish();
+}
+
+int64_t lqmpc_poly_controller_bytes(const lqmpc_poly_controller *c) { return c ? (int64_t)c->bytes : 0; }
+
+const char *lqmpc_poly_controller_kernel(const lqmpc_poly_controller *c) { return c ? "lqmpc_poly_ctl_step_kernel" : "none"; }
+
+int lqmpc_poly_controller_destroy(lqmpc_poly_controller *c)
+{
+    if (!c) return 0;
+    (void)hipSetDevice(c->h->device);
+    (void)hipStreamSynchronize(c->h->stream);
+    if (c->h->last_owner == c->id) set_last_kernel(c->h, "none");
+    pctl_free(c);
+    return 0;
+}
+
+}  // extern "C"

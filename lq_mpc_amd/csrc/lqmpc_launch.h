@@ -217,9 +217,30 @@ struct PolyParams {
     double *u0, *VN, *Uplan, *Xplan, *lam;   // T = 0: u0 and VN required, the others may be null
     double *JT, *X, *U;                   // T >= 1: JT required, X and U may be null
     int *status, *iters;                  // may be null
+    // the prepared controller (launch_poly_ctl); unused by launch_poly
+    double *rec;                          // record r at rec + r * rstride (poly_rec_layout)
+    long long rstride, nrec;              // doubles between records; records the controller holds
+    const int *idx;                       // factor: wavefront j writes record idx[j] (device; null: record j), an entry outside [0, nrec) is skipped
 };
 size_t poly_lds_bytes(int nx, int nu, int N, int m);
 bool poly_fits(int nx, int nu, int N, int m);
 bool launch_poly(const PolyParams &p, hipStream_t stream, const char **name);
+
+// ... its prepared controller (lqmpc_poly_controller_*).  One record per instance, contiguous, so that a wavefront reads it with
+// consecutive lanes on consecutive addresses: [A (nx nx) | B (nx nu) | W_k = A^k B, k < N (N nx nu) | Jp (n (n + 1) / 2)], Jp = L^-1
+// packed by rows, entry (j, t <= j) at j (j + 1) / 2 + t.  The stride is a multiple of 16 doubles: records start on 128-byte lines.
+struct PolyRec {
+    int A, B, W, Jp, stride;
+};
+__host__ __device__ constexpr PolyRec poly_rec_layout(int nx, int nu, int N)
+{
+    const int n = N * nu, A = 0, B = A + nx * nx, W = B + nx * nu, Jp = W + N * nx * nu, end = Jp + n * (n + 1) / 2;
+    return PolyRec{A, B, W, Jp, (end + 15) / 16 * 16};
+}
+// what: the factor launch (p.Bsz wavefronts over p.A, p.B instance-minor over p.Bsz; records through p.idx), one step from the
+// records (p.T = 0) or T closed-loop steps from them (p.T >= 1); p.sh holds Q, R, P, Fu and the references in every case
+enum { POLY_CTL_FACTOR = 0, POLY_CTL_STEP = 1, POLY_CTL_ROLLOUT = 2 };
+size_t poly_step_lds_bytes(int nx, int nu, int N, int m);
+bool launch_poly_ctl(const PolyParams &p, int what, hipStream_t stream, const char **name);
 
 }  // namespace lqmpc

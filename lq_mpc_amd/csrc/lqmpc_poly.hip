@@ -1,6 +1,6 @@
-// lqmpc_poly.hip -- the MPC problem with polytopic input constraints Fu u_i <= 1 (lqmpc_solve_poly_batch, lqmpc_rollout_poly_batch):
-// any (m, nu) matrix Fu, not only the rows of a box.  A kernel file of its own; it shares nothing with the box kernels but the
-// parameter conventions.  gfx950 (MI355X) only.
+// lqmpc_poly.hip -- the MPC problem with polytopic input constraints Fu u_i <= 1 (lqmpc_solve_poly_batch, lqmpc_rollout_poly_batch, and
+// the prepared controller lqmpc_poly_controller_*): any (m, nu) matrix Fu, not only the rows of a box.  A kernel file of its own; it
+// shares nothing with the box kernels but the parameter conventions.  gfx950 (MI355X) only.
 //
 // Per instance, with n = N nu:   min U'HU + 2g'U   s.t.  (I_N (x) Fu) U <= 1,   H = Gamma'Qbar Gamma + Rbar,  g = Gamma'Qbar (Phi x0 - xref) - Rbar uref.
 // Method: Goldfarb-Idnani, the dual active-set method from the unconstrained minimiser.  With G = 2H = LL' and J = L^-T (J J' = G^-1),
@@ -15,6 +15,13 @@
 // dynamic LDS (poly_lds: one layout function for host and device), J with row stride n | 1, the pristine J = L^-T and Rf packed.
 // Set-up, once per instance: W_k = A^k B, S_c = Q + A'S_{c+1}A, block (c1, c2 <= c1) of G = 2 B'S_c1 W_{c1-c2} (+ 2R), Cholesky, L^-1.
 // The linear term of a solve comes from one roll of the free response and the same W (no Fq matrix is kept).
+//
+// Prepared controller: the body has three phases -- the set-up, the solve at a state, the outputs or the plant step -- and five modes
+// that pick among them (PolyMode).  The factor kernel runs the set-up and writes one record [A | B | W | Jp] per instance
+// (poly_rec_layout); the step and the controller's rollout load the record where the one-shot kernels run the set-up, and from there
+// every mode runs the same statements on the same values, so a step returns the bits of the one-shot solve at the same state.  The
+// step solves once: it builds J straight from the record's Jp and keeps neither Jp, the plant nor the set-up's scratch in LDS
+// (poly_step_lds).
 //
 // No loop depends on the data for its termination: every loop has a bound the host knows, the passes of the active-set loop are counted
 // against max_iter, and the exits are written so that a NaN leaves the loop.  Non-finite data: status 2, found in the plan at the end.
@@ -68,6 +75,37 @@ __host__ __device__ inline PolyLds poly_lds(int nx, int nu, int N, int m)
     return o;
 }
 
+// The image of lqmpc_poly_ctl_step_kernel: poly_lds without the plant, the packed copy of L^-1 (read from the record, once), the
+// next state and the set-up's scratch.  The offsets left out are -1.
+__host__ __device__ inline PolyLds poly_step_lds(int nx, int nu, int N, int m)
+{
+    PolyLds o;
+    const int n = N * nu, tri = n * (n + 1) / 2;
+    o.ld = n | 1;
+    int e = 0;
+    o.Q = e; e += nx * nx;
+    o.P = e; e += nx * nx;
+    o.R = e; e += nu * nu;
+    o.Fh = e; e += m * nu;
+    o.bh = e; e += m;
+    o.A = e; e += nx * nx;
+    o.B = e; e += nx * nu;
+    o.At = o.Bt = o.Jp = o.xn = -1;
+    o.W = e; e += N * nx * nu;
+    o.J = e; e += n * o.ld;
+    int u = tri;                             // Rf packed by columns; linear term: y; V_N: the stage costs
+    if (u < N * nx + 1) u = N * nx + 1;
+    o.Rf = e; e += u;
+    o.X = e; e += (N + 1) * nx;
+    o.av = e; e += n;
+    o.U = e; e += n;
+    o.d = e; e += n;
+    o.xc = e; e += nx;
+    o.act = e; e += (N * m + 7) / 8;
+    o.total = e;
+    return o;
+}
+
 __device__ __forceinline__ double wave_sum(double v)
 {
     // a butterfly: every lane adds the same pairs, so every lane ends with the same bits
@@ -85,15 +123,35 @@ __device__ __forceinline__ void wave_argmax(double &v, int &i)
     }
 }
 
-template <bool ROLL>
+// What a kernel runs of the body's three phases (set-up | solve at a state | outputs or plant step):
+enum PolyMode {
+    POLY_SOLVE,                              // set-up, one solve, the outputs of a solve
+    POLY_ROLL,                               // set-up, T times: solve, plant step
+    POLY_FACTOR,                             // set-up, then the record [A | B | W | Jp] to HBM
+    POLY_STEP,                               // the record in the set-up's place, one solve, the outputs of a solve
+    POLY_CTL_ROLL                            // the record in the set-up's place, T times: solve, plant step
+};
+
+template <int MODE>
 __device__ __forceinline__ void poly_body(const PolyParams &p)
 {
     extern __shared__ double lds_poly[];
+    constexpr bool ROLL = MODE == POLY_ROLL || MODE == POLY_CTL_ROLL;
+    constexpr bool SETUP = MODE == POLY_SOLVE || MODE == POLY_ROLL || MODE == POLY_FACTOR;
     const int nx = p.nx, nu = p.nu, N = p.N, m = p.m, n = N * nu, Nm = N * m;
     const int t = threadIdx.x;
-    const PolyLds o = poly_lds(nx, nu, N, m);
+    const PolyLds o = MODE == POLY_STEP ? poly_step_lds(nx, nu, N, m) : poly_lds(nx, nu, N, m);
     const int ld = o.ld;
     const long long Bsz = p.Bsz, b = blockIdx.x;
+    // the record of this wavefront: the factor kernel writes record idx[b] of the controller's nrec (an entry outside is skipped
+    // whole, before anything is written), the step and the controller's rollout read record b
+    const PolyRec ro = poly_rec_layout(nx, nu, N);
+    long long slot = b;
+    if (MODE == POLY_FACTOR) {
+        if (p.idx) slot = p.idx[b];
+        if (slot < 0 || slot >= p.nrec) return;
+    }
+    double *rec = SETUP && MODE != POLY_FACTOR ? nullptr : p.rec + slot * p.rstride;
     const double *sh = p.sh;
     const double inf = __builtin_inf();
 
@@ -106,16 +164,22 @@ __device__ __forceinline__ void poly_body(const PolyParams &p)
     // ---- the data of the instance ----
     for (int e = t; e < nx * nx; e += POLY_THREADS) {
         Qs[e] = sh[p.so.Q + e]; Ps[e] = sh[p.so.P + e];
-        Am[e] = p.A[(long long)e * Bsz + b];
+        Am[e] = SETUP ? p.A[(long long)e * Bsz + b] : rec[ro.A + e];
         if (ROLL) Atm[e] = p.At[(long long)e * p.sE + b * p.sI];
     }
     for (int e = t; e < nu * nu; e += POLY_THREADS) Rs[e] = sh[p.so.R + e];
     for (int e = t; e < nx * nu; e += POLY_THREADS) {
-        Bm[e] = p.B[(long long)e * Bsz + b];
-        W[e] = Bm[e];
+        Bm[e] = SETUP ? p.B[(long long)e * Bsz + b] : rec[ro.B + e];
+        if (SETUP) W[e] = Bm[e];
         if (ROLL) Btm[e] = p.Bt[(long long)e * p.sE + b * p.sI];
     }
-    if (t < m) {
+    if (!SETUP) {
+        // consecutive lanes on consecutive addresses of the record
+        for (int e = t; e < N * nx * nu; e += POLY_THREADS) W[e] = rec[ro.W + e];
+        if (MODE == POLY_CTL_ROLL)
+            for (int e = t; e < n * (n + 1) / 2; e += POLY_THREADS) Jp[e] = rec[ro.Jp + e];
+    }
+    if (MODE != POLY_FACTOR && t < m) {
         double s = 0.0;
 #pragma unroll 4
         for (int c = 0; c < nu; ++c) s = __builtin_fma(sh[p.so.Fu + t * nu + c], sh[p.so.Fu + t * nu + c], s);
@@ -123,107 +187,121 @@ __device__ __forceinline__ void poly_body(const PolyParams &p)
         for (int c = 0; c < nu; ++c) Fh[t * nu + c] = sh[p.so.Fu + t * nu + c] * inv;
         bh[t] = inv;
     }
-    if (t < nx) xc[t] = p.x0[(long long)t * Bsz + b];
-    for (int e = t; e < Nm; e += POLY_THREADS) act[e] = 0;
+    if (MODE != POLY_FACTOR) {
+        if (t < nx) xc[t] = p.x0[(long long)t * Bsz + b];
+        for (int e = t; e < Nm; e += POLY_THREADS) act[e] = 0;
+    }
     __syncthreads();
     double rho = 0.0;                        // the distance of the farthest facet
-    for (int j = 0; j < m; ++j) rho = bh[j] > rho ? bh[j] : rho;
+    if (MODE != POLY_FACTOR)
+        for (int j = 0; j < m; ++j) rho = bh[j] > rho ? bh[j] : rho;
     const double tol = p.eps * rho;
 
-    // ---- set-up: W_k = A W_{k-1} ----
-    for (int k = 1; k < N; ++k) {
-        for (int e = t; e < nx * nu; e += POLY_THREADS) {
-            const int a = e / nu, c = e - a * nu;
-            double s = 0.0;
-#pragma unroll 4
-            for (int q = 0; q < nx; ++q) s = __builtin_fma(Am[a * nx + q], W[(k - 1) * nx * nu + q * nu + c], s);
-            W[k * nx * nu + e] = s;
-        }
-        __syncthreads();
-    }
-    // ---- the lower triangle of G = 2H, block row c1 from S_c1 = sum_{r >= c1} (A^{r-c1})'Q_r A^{r-c1}: S_{N-1} = P, S_c = Q + A'S_{c+1}A ----
-    {
-        double *S = Rf, *Tm = Rf + nx * nx, *SB = Rf + 2 * nx * nx;
-        for (int e = t; e < nx * nx; e += POLY_THREADS) S[e] = Ps[e];
-        __syncthreads();
-        for (int c1 = N - 1; c1 >= 0; --c1) {
+    if (SETUP) {
+        // ---- set-up: W_k = A W_{k-1} ----
+        for (int k = 1; k < N; ++k) {
             for (int e = t; e < nx * nu; e += POLY_THREADS) {
-                const int a = e / nu, k = e - a * nu;
+                const int a = e / nu, c = e - a * nu;
                 double s = 0.0;
 #pragma unroll 4
-                for (int q = 0; q < nx; ++q) s = __builtin_fma(S[a * nx + q], Bm[q * nu + k], s);
-                SB[e] = s;
+                for (int q = 0; q < nx; ++q) s = __builtin_fma(Am[a * nx + q], W[(k - 1) * nx * nu + q * nu + c], s);
+                W[k * nx * nu + e] = s;
             }
             __syncthreads();
-            if (t < n && t / nu <= c1) {
-                const int c2 = t / nu, k2 = t - c2 * nu;
-                const double *Wd = W + (c1 - c2) * nx * nu;
-                for (int k1 = 0; k1 < nu; ++k1) {
+        }
+        // ---- the lower triangle of G = 2H, block row c1 from S_c1 = sum_{r >= c1} (A^{r-c1})'Q_r A^{r-c1}: S_{N-1} = P, S_c = Q + A'S_{c+1}A ----
+        {
+            double *S = Rf, *Tm = Rf + nx * nx, *SB = Rf + 2 * nx * nx;
+            for (int e = t; e < nx * nx; e += POLY_THREADS) S[e] = Ps[e];
+            __syncthreads();
+            for (int c1 = N - 1; c1 >= 0; --c1) {
+                for (int e = t; e < nx * nu; e += POLY_THREADS) {
+                    const int a = e / nu, k = e - a * nu;
                     double s = 0.0;
 #pragma unroll 4
-                    for (int a = 0; a < nx; ++a) s = __builtin_fma(SB[a * nu + k1], Wd[a * nu + k2], s);
-                    if (c1 == c2) s += Rs[k1 * nu + k2];
-                    J[(c1 * nu + k1) * ld + t] = 2.0 * s;
-                }
-            }
-            if (c1 > 0) {
-                for (int e = t; e < nx * nx; e += POLY_THREADS) {
-                    const int a = e / nx, c = e - a * nx;
-                    double s = 0.0;
-#pragma unroll 4
-                    for (int q = 0; q < nx; ++q) s = __builtin_fma(S[a * nx + q], Am[q * nx + c], s);
-                    Tm[e] = s;
+                    for (int q = 0; q < nx; ++q) s = __builtin_fma(S[a * nx + q], Bm[q * nu + k], s);
+                    SB[e] = s;
                 }
                 __syncthreads();
-                for (int e = t; e < nx * nx; e += POLY_THREADS) {
-                    const int a = e / nx, c = e - a * nx;
-                    double s = Qs[e];
+                if (t < n && t / nu <= c1) {
+                    const int c2 = t / nu, k2 = t - c2 * nu;
+                    const double *Wd = W + (c1 - c2) * nx * nu;
+                    for (int k1 = 0; k1 < nu; ++k1) {
+                        double s = 0.0;
 #pragma unroll 4
-                    for (int q = 0; q < nx; ++q) s = __builtin_fma(Am[q * nx + a], Tm[q * nx + c], s);
-                    S[e] = s;
+                        for (int a = 0; a < nx; ++a) s = __builtin_fma(SB[a * nu + k1], Wd[a * nu + k2], s);
+                        if (c1 == c2) s += Rs[k1 * nu + k2];
+                        J[(c1 * nu + k1) * ld + t] = 2.0 * s;
+                    }
                 }
+                if (c1 > 0) {
+                    for (int e = t; e < nx * nx; e += POLY_THREADS) {
+                        const int a = e / nx, c = e - a * nx;
+                        double s = 0.0;
+#pragma unroll 4
+                        for (int q = 0; q < nx; ++q) s = __builtin_fma(S[a * nx + q], Am[q * nx + c], s);
+                        Tm[e] = s;
+                    }
+                    __syncthreads();
+                    for (int e = t; e < nx * nx; e += POLY_THREADS) {
+                        const int a = e / nx, c = e - a * nx;
+                        double s = Qs[e];
+#pragma unroll 4
+                        for (int q = 0; q < nx; ++q) s = __builtin_fma(Am[q * nx + a], Tm[q * nx + c], s);
+                        S[e] = s;
+                    }
+                }
+                __syncthreads();
             }
+        }
+        // ---- Cholesky factor G = LL' in place, column by column: lane i holds row i; the reciprocals of the diagonal go to d.  A pivot
+        // that is not positive gives NaN, nothing waits on it ----
+        for (int q = 0; q < n; ++q) {
+            double dq = J[q * ld + q];
+#pragma unroll 4
+            for (int k = 0; k < q; ++k) dq = __builtin_fma(-J[q * ld + k], J[q * ld + k], dq);
+            const double ri = 1.0 / sqrt(dq);
+            if (t < n && t > q) {
+                double s = J[t * ld + q];
+#pragma unroll 4
+                for (int k = 0; k < q; ++k) s = __builtin_fma(-J[t * ld + k], J[q * ld + k], s);
+                J[t * ld + q] = s * ri;
+            }
+            if (t == q) d[q] = ri;
             __syncthreads();
         }
-    }
-    // ---- Cholesky factor G = LL' in place, column by column: lane i holds row i; the reciprocals of the diagonal go to d.  A pivot
-    // that is not positive gives NaN, nothing waits on it ----
-    for (int q = 0; q < n; ++q) {
-        double dq = J[q * ld + q];
+        // ---- L^-1 in place, row by row: lane j holds column j ----
+        for (int i = 0; i < n; ++i) {
+            double s = 0.0;
+            if (t < i) {
 #pragma unroll 4
-        for (int k = 0; k < q; ++k) dq = __builtin_fma(-J[q * ld + k], J[q * ld + k], dq);
-        const double ri = 1.0 / sqrt(dq);
-        if (t < n && t > q) {
-            double s = J[t * ld + q];
-#pragma unroll 4
-            for (int k = 0; k < q; ++k) s = __builtin_fma(-J[t * ld + k], J[q * ld + k], s);
-            J[t * ld + q] = s * ri;
+                for (int k = t; k < i; ++k) s = __builtin_fma(J[i * ld + k], J[k * ld + t], s);
+                s = 0.0 - s * d[i];
+            }
+            __syncthreads();
+            if (t < i) J[i * ld + t] = s;
+            if (t == i) J[i * ld + i] = d[i];
+            __syncthreads();
         }
-        if (t == q) d[q] = ri;
+        if (t < n)
+            for (int j = t; j < n; ++j) Jp[j * (j + 1) / 2 + t] = J[j * ld + t];
         __syncthreads();
     }
-    // ---- L^-1 in place, row by row: lane j holds column j ----
-    for (int i = 0; i < n; ++i) {
-        double s = 0.0;
-        if (t < i) {
-#pragma unroll 4
-            for (int k = t; k < i; ++k) s = __builtin_fma(J[i * ld + k], J[k * ld + t], s);
-            s = 0.0 - s * d[i];
-        }
-        __syncthreads();
-        if (t < i) J[i * ld + t] = s;
-        if (t == i) J[i * ld + i] = d[i];
-        __syncthreads();
+    if (MODE == POLY_FACTOR) {
+        // ---- the record: consecutive lanes on consecutive addresses ----
+        for (int e = t; e < nx * nx; e += POLY_THREADS) rec[ro.A + e] = Am[e];
+        for (int e = t; e < nx * nu; e += POLY_THREADS) rec[ro.B + e] = Bm[e];
+        for (int e = t; e < N * nx * nu; e += POLY_THREADS) rec[ro.W + e] = W[e];
+        for (int e = t; e < n * (n + 1) / 2; e += POLY_THREADS) rec[ro.Jp + e] = Jp[e];
+        return;
     }
-    if (t < n)
-        for (int j = t; j < n; ++j) Jp[j * (j + 1) / 2 + t] = J[j * ld + t];
-    __syncthreads();
 
-    // J = L^-T from the packed copy: what a solve starts from
+    // J = L^-T from the packed copy: what a solve starts from (the step reads the record's copy, once)
+    const double *Jsrc = MODE == POLY_STEP ? rec + ro.Jp : Jp;
     auto pristine = [&]() {
         if (t < n)
 #pragma unroll 4
-            for (int j = 0; j < n; ++j) J[t * ld + j] = j >= t ? Jp[j * (j + 1) / 2 + t] : 0.0;
+            for (int j = 0; j < n; ++j) J[t * ld + j] = j >= t ? Jsrc[j * (j + 1) / 2 + t] : 0.0;
         __syncthreads();
     };
     pristine();
@@ -543,12 +621,28 @@ __device__ __forceinline__ void poly_body(const PolyParams &p)
 
 }  // namespace
 
-__global__ void __launch_bounds__(POLY_THREADS) lqmpc_poly_solve_kernel(const PolyParams p) { poly_body<false>(p); }
-__global__ void __launch_bounds__(POLY_THREADS) lqmpc_poly_rollout_kernel(const PolyParams p) { poly_body<true>(p); }
+__global__ void __launch_bounds__(POLY_THREADS) lqmpc_poly_solve_kernel(const PolyParams p) { poly_body<POLY_SOLVE>(p); }
+__global__ void __launch_bounds__(POLY_THREADS) lqmpc_poly_rollout_kernel(const PolyParams p) { poly_body<POLY_ROLL>(p); }
+__global__ void __launch_bounds__(POLY_THREADS) lqmpc_poly_ctl_factor_kernel(const PolyParams p) { poly_body<POLY_FACTOR>(p); }
+__global__ void __launch_bounds__(POLY_THREADS) lqmpc_poly_ctl_step_kernel(const PolyParams p) { poly_body<POLY_STEP>(p); }
+__global__ void __launch_bounds__(POLY_THREADS) lqmpc_poly_ctl_rollout_kernel(const PolyParams p) { poly_body<POLY_CTL_ROLL>(p); }
 
 size_t poly_lds_bytes(int nx, int nu, int N, int m) { return sizeof(double) * (size_t)poly_lds(nx, nu, N, m).total; }
+size_t poly_step_lds_bytes(int nx, int nu, int N, int m) { return sizeof(double) * (size_t)poly_step_lds(nx, nu, N, m).total; }
 
 bool poly_fits(int nx, int nu, int N, int m) { return poly_lds_bytes(nx, nu, N, m) <= POLY_LDS_LIMIT; }
+
+// an image over 64 KiB needs the kernel function's leave
+static bool poly_lds_attr(const void *fn, size_t bytes)
+{
+    if (bytes <= 64 * 1024) return true;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) {
+        fprintf(stderr, "lqmpc: hipFuncSetAttribute(%zu bytes of LDS): %s\n", bytes, hipGetErrorString(e));
+        return false;
+    }
+    return true;
+}
 
 bool launch_poly(const PolyParams &p, hipStream_t stream, const char **name)
 {
@@ -556,16 +650,32 @@ bool launch_poly(const PolyParams &p, hipStream_t stream, const char **name)
     const bool roll = p.T > 0;
     const void *fn = roll ? (const void *)lqmpc_poly_rollout_kernel : (const void *)lqmpc_poly_solve_kernel;
     const size_t bytes = poly_lds_bytes(p.nx, p.nu, p.N, p.m);
-    if (bytes > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) {
-            fprintf(stderr, "lqmpc: hipFuncSetAttribute(%zu bytes of LDS): %s\n", bytes, hipGetErrorString(e));
-            return false;
-        }
-    }
+    if (!poly_lds_attr(fn, bytes)) return false;
     if (roll) hipLaunchKernelGGL(lqmpc_poly_rollout_kernel, dim3((unsigned)p.Bsz), dim3(POLY_THREADS), bytes, stream, p);
     else hipLaunchKernelGGL(lqmpc_poly_solve_kernel, dim3((unsigned)p.Bsz), dim3(POLY_THREADS), bytes, stream, p);
     *name = roll ? "lqmpc_poly_rollout_kernel" : "lqmpc_poly_solve_kernel";
+    return true;
+}
+
+bool launch_poly_ctl(const PolyParams &p, int what, hipStream_t stream, const char **name)
+{
+    if (p.Bsz < 1 || p.N * p.nu > POLY_THREADS || !poly_fits(p.nx, p.nu, p.N, p.m) || !p.rec || p.rstride < poly_rec_layout(p.nx, p.nu, p.N).stride)
+        return false;
+    const dim3 grid((unsigned)p.Bsz), block(POLY_THREADS);
+    const size_t full = poly_lds_bytes(p.nx, p.nu, p.N, p.m), step = poly_step_lds_bytes(p.nx, p.nu, p.N, p.m);
+    if (what == POLY_CTL_FACTOR) {
+        if (p.nrec < 1 || !poly_lds_attr((const void *)lqmpc_poly_ctl_factor_kernel, full)) return false;
+        hipLaunchKernelGGL(lqmpc_poly_ctl_factor_kernel, grid, block, full, stream, p);
+        *name = "lqmpc_poly_ctl_factor_kernel";
+    } else if (what == POLY_CTL_STEP) {
+        if (p.T != 0 || !poly_lds_attr((const void *)lqmpc_poly_ctl_step_kernel, step)) return false;
+        hipLaunchKernelGGL(lqmpc_poly_ctl_step_kernel, grid, block, step, stream, p);
+        *name = "lqmpc_poly_ctl_step_kernel";
+    } else if (what == POLY_CTL_ROLLOUT) {
+        if (p.T < 1 || !poly_lds_attr((const void *)lqmpc_poly_ctl_rollout_kernel, full)) return false;
+        hipLaunchKernelGGL(lqmpc_poly_ctl_rollout_kernel, grid, block, full, stream, p);
+        *name = "lqmpc_poly_ctl_rollout_kernel";
+    } else return false;
     return true;
 }
 

@@ -922,6 +922,161 @@ class BatchController:
             pass
 
 
+class PolyBatchController:
+    """A prepared controller for a batch under F_u u_i <= 1, any (m, nu) matrix F_u (include/lqmpc.h, lqmpc_poly_controller_*): the
+    per-instance set-up of solve_poly_batch is computed once and kept in HBM, one record per instance; every step() solves one
+    polytope QP per instance at the states it is given, in one launch.  For closed loops the caller owns.  A step returns the bits
+    solve_poly_batch returns at the same state, and leaves nothing behind: no warm start across steps.
+
+    A, B: numpy arrays (nx, nx, Bsz) / (nx, nu, Bsz) or device tensors of those shapes (anything with .shape and .data_ptr()).
+    eps is the solver's option as it is NOW, max_iter is fixed here (0: 10 N nu + 20); the controller keeps the solver alive and
+    must be closed before it."""
+
+    def __init__(self, solver, N, A, B, Q, R, P, F_u, x_ref=None, u_ref=None, max_iter=0):
+        self._c = None
+        if not isinstance(solver, BatchSolver):
+            raise _lib.LqmpcError("PolyBatchController needs a BatchSolver (one GPU, one stream)")
+        self._solver = solver
+        self._L = solver._L
+        on_device = hasattr(A, "data_ptr")
+        if on_device:
+            sa, sb = tuple(A.shape), tuple(B.shape)
+            if len(sa) != 3 or len(sb) != 3 or sa[0] != sa[1] or sb[0] != sa[0] or sb[2] != sa[2]:
+                raise ValueError("A must be (nx,nx,Bsz) and B (nx,nu,Bsz), instance-minor")
+            if not (A.is_contiguous() and B.is_contiguous()) or "float64" not in str(A.dtype) or "float64" not in str(B.dtype):
+                raise ValueError("device A and B must be contiguous float64")
+            nx, nu, Bsz = sa[0], sb[1], sa[2]
+        else:
+            A, B, nx, nu, Bsz = BatchSolver._dims(A, B)
+        self.N, self.nx, self.nu, self.Bsz = int(N), nx, nu, Bsz
+        Q, R, P = _f64(Q, (nx, nx)), _f64(R, (nu, nu)), _f64(P, (nx, nx))
+        F_u = BatchSolver._Fu(F_u, nu)
+        self.m = F_u.shape[0]
+        x_ref, u_ref = _ref_or_none(x_ref, nx, self.N), _ref_or_none(u_ref, nu, self.N)
+        c = ctypes.c_void_p()
+        make = self._L.lqmpc_poly_controller_create_dev if on_device else self._L.lqmpc_poly_controller_create
+        _lib.check(make(solver._h, nx, nu, self.N, Bsz, _ptr(A), _ptr(B), _ptr(Q), _ptr(R), _ptr(P), _ptr(F_u), self.m,
+                        _ptr(x_ref), _ptr(u_ref), int(max_iter), ctypes.byref(c)))
+        self._c = c
+        self.model_version = 0                  # counts set_model calls
+        self.reference_version = 0              # ... and set_reference calls
+
+    def _live(self):
+        if self._c is None or not self._c.value:
+            raise _lib.LqmpcError("the controller is closed")
+        return self._c
+
+    def step(self, x, want_plan=False, want_lam=False):
+        """One polytope QP per instance at the states x (nx, Bsz), host arrays in and out: the dict of
+        BatchSolver.solve_poly_batch, bit for bit what it returns at x0 = x."""
+        c, nx, nu, N, Bsz = self._live(), self.nx, self.nu, self.N, self.Bsz
+        x = _f64(x, (nx, Bsz))
+        u0 = np.empty((nu, Bsz)); VN = np.empty(Bsz)
+        status = np.empty(Bsz, dtype=np.int32); iters = np.empty(Bsz, dtype=np.int32)
+        Up = np.empty((nu, N, Bsz)) if want_plan else None
+        Xp = np.empty((nx, N + 1, Bsz)) if want_plan else None
+        lam = np.empty((self.m, N, Bsz)) if want_lam else None
+        _lib.check(self._L.lqmpc_poly_controller_step(c, _ptr(x), _ptr(u0), _ptr(VN), _ptr(Up), _ptr(Xp), _ptr(lam), _ptr(status),
+                                                      _ptr(iters)))
+        out = {"u_0": u0, "V_N": VN, "status": status, "iters": iters}
+        if want_plan:
+            out["U_plan"], out["X_plan"] = Up, Xp
+        if want_lam:
+            out["lam"] = lam
+        return out
+
+    def step_dev(self, dx, du0, dVN=None, dUplan=None, dXplan=None, dlam=None, dstatus=None, diters=None):
+        """Device pointers / tensors; one launch enqueued on the solver's stream, returns at once.  dlam is (m, N, Bsz)."""
+        _lib.check(self._L.lqmpc_poly_controller_step_dev(self._live(), _ptr(dx), _ptr(du0), _ptr(dVN), _ptr(dUplan), _ptr(dXplan),
+                                                          _ptr(dlam), _ptr(dstatus), _ptr(diters)))
+
+    def rollout(self, T, x0, A_true, B_true, want_traj=False):
+        """T closed-loop steps of every instance from x0 (nx, Bsz) in one launch, from the controller's records and current
+        references: the dict of BatchSolver.rollout_poly_batch, bit for bit.  A_true (nx, nx) / B_true (nx, nu): one plant for the
+        batch; (nx, nx, Bsz) / (nx, nu, Bsz): one per instance.  Read-only on the controller."""
+        c, nx, nu, Bsz, T = self._live(), self.nx, self.nu, self.Bsz, int(T)
+        x0 = _f64(x0, (nx, Bsz))
+        A_true, B_true, per_inst = BatchSolver._plant(A_true, B_true, nx, nu, Bsz)
+        JT = np.empty(Bsz)
+        X = np.empty((nx, T + 1, Bsz)) if want_traj and T >= 1 else None
+        U = np.empty((nu, T, Bsz)) if want_traj and T >= 1 else None
+        status = np.empty(Bsz, dtype=np.int32); iters = np.empty(Bsz, dtype=np.int32)
+        _lib.check(self._L.lqmpc_poly_controller_rollout(c, T, _ptr(x0), _ptr(A_true), _ptr(B_true), per_inst,
+                                                         _ptr(JT), _ptr(X), _ptr(U), _ptr(status), _ptr(iters)))
+        return {"J_T": JT, "X": X, "U": U, "status": status, "iters": iters}
+
+    def rollout_dev(self, T, dx0, A_true, B_true, dJT, dX=None, dU=None, dstatus=None, diters=None, true_per_instance=False):
+        """Device pointers / tensors; enqueued on the solver's stream, returns at once.  A shared plant (true_per_instance=False)
+        is a pair of HOST arrays (nx, nx) / (nx, nu); a per-instance plant a pair of device arrays (nx, nx, Bsz) / (nx, nu, Bsz)."""
+        if not true_per_instance:
+            A_true, B_true = _f64(A_true, (self.nx, self.nx)), _f64(B_true, (self.nx, self.nu))
+        _lib.check(self._L.lqmpc_poly_controller_rollout_dev(self._live(), int(T), _ptr(dx0), _ptr(A_true), _ptr(B_true),
+                                                             1 if true_per_instance else 0, _ptr(dJT), _ptr(dX), _ptr(dU),
+                                                             _ptr(dstatus), _ptr(diters)))
+
+    def set_reference(self, x_ref=None, u_ref=None):
+        """New references (nx, N) / (nu, N) for every later step and rollout; None means zeros.  No record depends on them, so no
+        kernel runs: one copy on the solver's stream, ordered with the steps; the arrays are copied before this returns.  Every call
+        raises reference_version by one."""
+        c = self._live()
+        self.reference_version += 1
+        x_ref, u_ref = _ref_or_none(x_ref, self.nx, self.N), _ref_or_none(u_ref, self.nu, self.N)
+        _lib.check(self._L.lqmpc_poly_controller_set_reference(c, _ptr(x_ref), _ptr(u_ref)))
+
+    def set_model(self, A, B, idx=None):
+        """New models for some or all instances, in place, as BatchController.set_model takes them: A (nx, nx, m), B (nx, nu, m),
+        instance-minor over the update, for the instances idx (m distinct integers in [0, Bsz); None: all of them in order).  Numpy
+        arrays: checked here, copied before this returns.  Device tensors (idx an int32 device tensor of length m or None): enqueued
+        like a step, returns at once.  The listed records are factored again; the others keep every bit.  Every call raises
+        model_version by one."""
+        c = self._live()
+        if hasattr(A, "data_ptr") != hasattr(B, "data_ptr"):
+            raise ValueError("A and B must both be numpy arrays or both be device tensors")
+        self.model_version += 1
+        if not hasattr(A, "data_ptr"):
+            A, B, idx, m = _model_update_args(self.nx, self.nu, self.Bsz, A, B, idx)
+            _lib.check(self._L.lqmpc_poly_controller_set_model(c, m, _ptr(idx), _ptr(A), _ptr(B)))
+            return
+        sa, sb = tuple(A.shape), tuple(B.shape)
+        if len(sa) != 3 or sa[:2] != (self.nx, self.nx) or sb != (self.nx, self.nu, sa[2]):
+            raise ValueError(f"A must be ({self.nx}, {self.nx}, m) and B ({self.nx}, {self.nu}, m), got {sa} and {sb}")
+        if not (A.is_contiguous() and B.is_contiguous()) or "float64" not in str(A.dtype) or "float64" not in str(B.dtype):
+            raise ValueError("device A and B must be contiguous float64")
+        m = sa[2]
+        if idx is None:
+            if m != self.Bsz:
+                raise ValueError(f"idx=None replaces every model: m must be Bsz = {self.Bsz}, got {m}")
+        elif not hasattr(idx, "data_ptr") or tuple(idx.shape) != (m,) or "int32" not in str(idx.dtype) or not idx.is_contiguous():
+            raise ValueError(f"with device A and B, idx must be a contiguous int32 device tensor of length {m}")
+        _lib.check(self._L.lqmpc_poly_controller_set_model_dev(c, m, _ptr(idx), _ptr(A), _ptr(B)))
+
+    @property
+    def kernel(self):
+        return self._L.lqmpc_poly_controller_kernel(self._live()).decode()
+
+    @property
+    def nbytes(self):
+        return int(self._L.lqmpc_poly_controller_bytes(self._live()))
+
+    def close(self):
+        if getattr(self, "_c", None) is not None and self._c.value:
+            if self._solver._h.value:                     # (a closed solver has taken its stream with it: nothing left to wait for)
+                self._L.lqmpc_poly_controller_destroy(self._c)
+            self._c = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PlanVariable:
     """Stands where the reference keeps its cp.Variable: `.value` is None before the first solve, then the optimal plan."""
 
