@@ -32,7 +32,8 @@ __global__ void __launch_bounds__(64, (R16Build<NX, NU, N, LPI>::WAVES)) lqmpc_r
 {
     using C = R16<NX, NU, N, LPI, (R16Build<NX, NU, N, LPI>::OCC == 2)>;
     __shared__ double lds_raw[C::IPW * C::INST];
-    r16_body<NX, NU, N, MODE, LPI, R16Build<NX, NU, N, LPI>::OCC, (MODE == MODE_ROLLOUT && R16Build<NX, NU, N, LPI>::CHUNKS)>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
+    r16_body<NX, NU, N, MODE, LPI, R16Build<NX, NU, N, LPI>::OCC, (MODE == MODE_ROLLOUT && R16Build<NX, NU, N, LPI>::CHUNKS), false,
+             (MODE == MODE_ROLLOUT && R16Build<NX, NU, N, LPI>::ONE_TRIP)>(p, lds_raw, (long long)blockIdx.x * C::IPW, p.Bsz);
 }
 
 // MODE_SOLVE with the whole plan written out (p.Uplan): a kernel of its own, so that lqmpc_r16_kernel<.., MODE_SOLVE, ..> holds none of it

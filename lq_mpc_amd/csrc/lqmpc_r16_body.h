@@ -87,6 +87,9 @@ struct R16Build {
     // iteration-free closed-loop steps in speculative chunks: the rollout kernels of the throughput build in which they were measured
     // as a gain -- C3 (four instances per wavefront) and C4 (one) -- and no other
     static constexpr bool CHUNKS = NX == 4 && NU == 2 && ((LPI == 16 && N == 10) || (LPI == 64 && N == 20));
+    // the set-up with one round of global loads and P built inside the sweep (lqmpc_r16_setup.h, ONE_TRIP): the rollout kernel in which
+    // it was measured -- C3 -- and no other
+    static constexpr bool ONE_TRIP = NX == 4 && NU == 2 && LPI == 16 && N == 10;
 };
 
 // ---- the per-instance primitives in the two mappings ----
@@ -171,7 +174,11 @@ __device__ __forceinline__ unsigned row_umax(unsigned x)
 // PLAN (MODE_SOLVE, MODE_CTL_STEP): the instantiation behind lqmpc_solve_plan_batch / lqmpc_controller_step_plan, which also stores
 // the whole plan (p.Uplan, p.Xplan).  A kernel of its own, picked by the host: with PLAN = false nothing of it is compiled in, so
 // the plain calls run the code they ran before the plan existed.
-template <int NX, int NU, int N, int MODE, int LPI = 16, int OCC = 1, bool CHUNKS = false, bool PLAN = false>
+// ONE_TRIP (MODE_ROLLOUT, four instances per wavefront): between entry and the first closed-loop step one load only waits for another
+// one's result -- the permutation, fetched once; what the closed loop needs of the shared block and of the instance (its rows of the
+// plant and the weights, the box, x0) is loaded around that trip and parked in the LDS constants region across the set-up, and P is
+// built inside the set-up's sweep instead of by the call behind it.
+template <int NX, int NU, int N, int MODE, int LPI = 16, int OCC = 1, bool CHUNKS = false, bool PLAN = false, bool ONE_TRIP = false>
 __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long long slot0, long long slot_end)
 {
     constexpr bool PACKED = (OCC == 2);
@@ -179,6 +186,9 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
     constexpr int CS = C::CS;
     constexpr int n = C::n, RB = C::RB, LDW = C::LDW;
     constexpr int REC = NX * NX + NX * NU + NX;
+    // ONE_TRIP: what is parked in the constants region across the set-up -- the per-lane rows [A_true B_true | Q | R] of lanes i < NX / i < NU,
+    // then x0 | lb | ub
+    constexpr int PK_RW = 2 * NX + 2 * NU, PK_X = (NX > NU ? NX : NU) * PK_RW;
     const int lane = threadIdx.x, q = lane / LPI, i = lane % LPI;
     ldsd *L = (ldsd *)lds_raw + q * C::INST;
     ldsd *Pp = L + C::oP, *Wp = L + C::oW, *rL = L + C::oR, *xL = L + C::oX, *yL = L + C::oY;
@@ -187,7 +197,11 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
     const long long b_raw = slot0 + q;
     const bool valid = b_raw < slot_end;
     const long long slot = valid ? b_raw : slot_end - 1;
-    const long long b = p.perm ? (long long)p.perm[slot] : slot;
+    // (ONE_TRIP: the permutation's load is issued here and first looked at inside the set-up, behind the loads of the shared block)
+    int b_perm = 0;
+    if constexpr (ONE_TRIP) { if (p.perm) b_perm = p.perm[slot]; }
+    long long b = slot;
+    if constexpr (!ONE_TRIP) b = p.perm ? (long long)p.perm[slot] : slot;
     const double *sh = p.sh;
     const mask_t nmask = (n == 64) ? ~0ull : ((1ull << n) - 1ull);
 
@@ -274,7 +288,8 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
         if constexpr (LPI == 16) {
             const int gq = (lane >> 2) & 3;
             const long long sraw = slot0 + gq, sl = sraw < slot_end ? sraw : slot_end - 1;
-            bg = p.perm ? (long long)p.perm[sl] : sl;
+            if constexpr (ONE_TRIP) bg = sl;         // (with a permutation: from b, inside the set-up)
+            else bg = p.perm ? (long long)p.perm[sl] : sl;
             Lg = (ldsd *)lds_raw + gq * C::INST;
         }
         if constexpr (NX > 8) {
@@ -289,8 +304,54 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
                 }
             }
             __syncthreads();
+        } else if constexpr (ONE_TRIP) {
+            static_assert(MODE == MODE_ROLLOUT && LPI == 16 && ROLL && !LAZY_P, "one round of loads: the rollout of the four-instance mapping");
+            static_assert(PK_X + NX + 2 * NU <= C::CN + (C::CN & 1) && NX + 2 * NU <= LPI, "the parked values fit the constants region, one per lane");
+            // my row of [A_true B_true | Q | R] (lane i < NX / i < NU, as the closed loop holds them), one value of the box or of x0 per lane:
+            // what comes from the shared block is issued here, ahead of everything that waits for the permutation
+            const int ia = i < NX ? i : 0, ik = i < NU ? i : 0, eb = i - NX;
+            const bool tpi = p.true_per_instance != 0, isbox = eb >= 0 && eb < 2 * NU;
+            double rowv[PK_RW];
+#pragma unroll
+            for (int c = 0; c < NX; ++c) rowv[NX + NU + c] = sh[p.so.Q + ia * NX + c];
+#pragma unroll
+            for (int k = 0; k < NU; ++k) rowv[2 * NX + NU + k] = sh[p.so.R + ik * NU + k];
+            if (!tpi) {
+#pragma unroll
+                for (int c = 0; c < NX; ++c) rowv[c] = sh[p.so.At + ia * NX + c];
+#pragma unroll
+                for (int k = 0; k < NU; ++k) rowv[NX + k] = sh[p.so.Bt + ia * NU + k];
+            }
+            const double boxv = sh[isbox ? (eb < NU ? p.so.lb + eb : p.so.ub + eb - NU) : p.so.lb];
+            auto late_bg = [&]() -> long long {
+                // the instance of my MFMA block: the value its lanes 16 gq .. hold in b (the same clamp for a ragged last wavefront)
+                if (!p.perm) return bg;
+                const int bi = b_perm;
+                b = (long long)b_perm;
+                const int b0 = __builtin_amdgcn_readlane(bi, 0), b1 = __builtin_amdgcn_readlane(bi, 16);
+                const int b2 = __builtin_amdgcn_readlane(bi, 32), b3 = __builtin_amdgcn_readlane(bi, 48);
+                const int gq = (lane >> 2) & 3;
+                return (long long)(gq == 0 ? b0 : (gq == 1 ? b1 : (gq == 2 ? b2 : b3)));
+            };
+            auto late_park = [&]() {
+                // ... and what is the instance's own, in the same batch as the model tiles; then everything to LDS (predicated stores: the dummy slot)
+                if (tpi) {
+#pragma unroll
+                    for (int c = 0; c < NX; ++c) rowv[c] = p.At[(long long)(ia * NX + c) * Bsz + b];
+#pragma unroll
+                    for (int k = 0; k < NU; ++k) rowv[NX + k] = p.Bt[(long long)(ia * NU + k) * Bsz + b];
+                }
+                const double x0v = p.rec ? p.rec[b * REC + NX * NX + NX * NU + ia] : p.x0[(long long)ia * Bsz + b];
+                ldsd *pk = L + C::oC;
+                const bool own = i < NX || i < NU;
+#pragma unroll
+                for (int e = 0; e < PK_RW; ++e) pk[own ? i * PK_RW + e : C::oD - C::oC] = rowv[e];
+                pk[(i < NX || isbox) ? PK_X + i : C::oD - C::oC] = i < NX ? x0v : boxv;
+            };
+            const LateT<decltype(late_bg), decltype(late_park)> late{late_bg, late_park};
+            r16_setup_mfma<NX, NU, N, LPI, PACKED, RB, ROLL, true, true>(setup_args(p), bg, Lg, L, C::oW, C::oG, C::oD, G, roll_args(p), cold32[0], cold32[1], C::oP, late);
         } else r16_setup_mfma<NX, NU, N, LPI, PACKED, RB, ROLL>(setup_args(p), bg, Lg, L, C::oW, C::oG, C::oD, G, roll_args(p), cold32[0], cold32[1]);
-        if constexpr (!LAZY_P) r16_build_P<NX, NU, N, LPI, PACKED>(setup_args(p), bg, Lg, C::oP, C::oD);
+        if constexpr (!LAZY_P && !ONE_TRIP) r16_build_P<NX, NU, N, LPI, PACKED>(setup_args(p), bg, Lg, C::oP, C::oD);
         RPROF(5);
         // constant part of the unconstrained minimiser: v_r = -W (2 gref + P centre) = -2 W gref - centre (references / off-centre boxes only)
         const bool has_lin = p.has_lin != 0;
@@ -476,8 +537,14 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
 #pragma unroll
     for (int s = 0; s < RB; ++s) {
         const int k = rw[s] % NU;
+        if constexpr (ONE_TRIP) {
+            const double lbk = L[C::oC + PK_X + NX + k], ubk = L[C::oC + PK_X + NX + NU + k];
+            h[s] = vrow[s] ? 0.5 * (ubk - lbk) : 1.0;
+            ctr[s] = vrow[s] ? 0.5 * (ubk + lbk) : 0.0;
+        } else {
         h[s] = vrow[s] ? 0.5 * (sh[p.so.ub + k] - sh[p.so.lb + k]) : 1.0;
         ctr[s] = vrow[s] ? 0.5 * (sh[p.so.ub + k] + sh[p.so.lb + k]) : 0.0;
+        }
     }
     // stage weights of the open-loop value function once (the closed loop keeps its rows of them per lane, see below)
     double Qm[NX][NX], Rm[NU][NU];
@@ -1348,11 +1415,18 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
 #pragma unroll
         for (int a = 0; a < NX; ++a) {
             if constexpr (CTL_R) x[a] = p.x0[(long long)a * Bsz + bq];
+            else if constexpr (ONE_TRIP) x[a] = L[C::oC + PK_X + a];
             else x[a] = p.rec ? p.rec[bq * REC + NX * NX + NX * NU + a] : p.x0[(long long)a * Bsz + bq];
         }
         int ia = i < NX ? i : 0, ik = i < NU ? i : 0;
         asm volatile("" : "+v"(ia), "+v"(ik));          // (opaque: or these loads are issued at the top and their results spilled across the set-up)
         double Qr_[NX], Ar_[NX], Br_[NU], Rr_[NU];
+        if constexpr (ONE_TRIP) {                       // (parked ahead of the set-up; the row of R is the one lane ik parked)
+#pragma unroll
+            for (int c = 0; c < NX; ++c) { Qr_[c] = L[C::oC + ia * PK_RW + NX + NU + c]; Ar_[c] = L[C::oC + ia * PK_RW + c]; }
+#pragma unroll
+            for (int k = 0; k < NU; ++k) { Br_[k] = L[C::oC + ia * PK_RW + NX + k]; Rr_[k] = L[C::oC + ik * PK_RW + 2 * NX + NU + k]; }
+        } else {
 #pragma unroll
         for (int c = 0; c < NX; ++c) {
             Qr_[c] = sh[p.so.Q + ia * NX + c];
@@ -1362,6 +1436,7 @@ __device__ __forceinline__ void r16_body(const KParams &p, double *lds_raw, long
         for (int k = 0; k < NU; ++k) {
             Br_[k] = p.true_per_instance ? p.Bt[(long long)(ia * NU + k) * Bsz + bq] : sh[p.so.Bt + ia * NU + k];
             Rr_[k] = sh[p.so.R + ik * NU + k];
+        }
         }
         // my rows: in registers up to 24 of them (C3 0.325 -> 0.318 ms, C4 4.30 -> 4.14 ms: the free steps of a rollout read nothing from
         // LDS); the larger state dimensions of the one-instance-per-wavefront build keep them in the LDS constants region (the open-loop

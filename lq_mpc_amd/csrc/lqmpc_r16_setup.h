@@ -332,22 +332,80 @@ __device__ __attribute__((noinline)) void r16_build_P(const SetupArgs p, long lo
 // outside the set-up; both zero: no guess.
 //
 // READ_G = false (the wide states, r16_setup_wide below): G stays in LDS at oG, which then must not alias W; the caller reads it back.
-template <int NX, int NU, int N, int LPI, bool PACKED, int RB, bool ROLL = false, bool READ_G = true>
+//
+// ONE_TRIP (the kernels it was measured in: R16Build::ONE_TRIP; ROLL, LPI = 16): one round of global loads and no call.
+//   * Everything read from the batch-shared block (Q, P_T, R, the box) is issued first; then late.bg() hands over the instance of the
+//     block -- the one value of the set-up that waits for the permutation -- and the model tiles and x0 follow in one batch;
+//     late.park() runs behind them (the caller's own loads, issued around the same trip, go to LDS there).
+//   * P is built here, from the tiles the sweep holds anyway, with the products of r16_build_P in its order and with its accumulator
+//     operands (P in LDS is the same, bit for bit): the Lt recursion and the operands ap ride in the stage loop (both run
+//     j = N-1 .. 0), the powers X_d, the diagonal accumulators and the tile stores of P stand with the roll and the tile stores of W.
+//     (A tile)' is formed once, by a product with the identity, for the roll and for the powers.
+//   * The roll always runs (its flags are dropped where the guess does not apply), so that the sweep's tail, the roll, P and the
+//     stores of W are one block of straight-line code.
+struct NoLate {
+    __device__ __forceinline__ long long bg() const { return 0; }
+    __device__ __forceinline__ void park() const {}
+};
+template <class FB, class FP>
+struct LateT {
+    const FB &fb;
+    const FP &fp;
+    __device__ __forceinline__ long long bg() const { return fb(); }
+    __device__ __forceinline__ void park() const { fp(); }
+};
+template <int NX, int NU, int N, int LPI, bool PACKED, int RB, bool ROLL = false, bool READ_G = true, bool ONE_TRIP = false, class Late = NoLate>
 __device__ __forceinline__ void r16_setup_mfma(const SetupArgs &p, long long bg, wg::ldsd *Lg, wg::ldsd *Lq, int oW, int oG, int oD,
-                                              double (&G)[RB][NX], const RollArgs &ra, unsigned &coldL, unsigned &coldU)
+                                              double (&G)[RB][NX], const RollArgs &ra, unsigned &coldL, unsigned &coldU, int oP = 0,
+                                              const Late &late = Late())
 {
     static_assert(!ROLL || (LPI == 16 && N * NU <= 32), "the cold-start roll serves the four-instance mapping");
     static_assert(READ_G || !ROLL, "the roll runs under the read-back of G");
+    static_assert(!ONE_TRIP || (ROLL && LPI == 16), "one round of loads: the four-instance mapping with the roll");
     using T = SetupT<NX, NU, N, LPI>;
     constexpr int n = T::n, NT = T::NT, SPT = T::SPT, NTM = T::NTM, TX = T::TX, NUP = T::NUP;
     const int lane = threadIdx.x, r = lane >> 4, c = lane & 3, g = (lane >> 2) & 3;
     wg::ldsd *Wp = Lg + oW, *Gs = Lg + oG;
     const int dW = oD - oW, dG = oD - oG;
     // ---- the model and the weights as register matrices (tiles [a][b]: rows 4a.., columns 4b..) ----
-    const ModelLd<NX, NU> ld(p, bg);
     double A[TX][TX], Q[TX][TX], S[TX][TX];
     double Bp[TX], nBt[TX];                                           // B (n_x x 4, columns 0..NU-1) by row tiles; -(B tile)' as register matrices
     double Bpl[SPT][TX], nBpl[SPT][TX];                               // B (and -B) in column block q of a tile
+    double Rp;
+    double Rd = 0.0, hk1 = 1.0, x0r[TX];                              // ONE_TRIP: R on the diagonal blocks of a diagonal tile, the roll's half-width and x0
+    if constexpr (ONE_TRIP) {
+        const ModelLd<NX, NU> sl(p, 0);                               // (the shared block only: S() takes nothing of the instance)
+#pragma unroll
+        for (int a = 0; a < TX; ++a)
+#pragma unroll
+            for (int b = 0; b < TX; ++b) { Q[a][b] = sl.S(p.oQ, 4 * a + r, 4 * b + c, NX); S[a][b] = sl.S(p.oP, 4 * a + r, 4 * b + c, NX); }
+        Rp = (r == c && r >= NU && r < NUP) ? 1.0 : sl.S(p.oR, r, c, NU);
+#pragma unroll
+        for (int qq = 0; qq < SPT; ++qq) {
+            const int rr = r - qq * NUP, cc = c - qq * NUP;
+            const double x = sl.S(p.oR, rr, cc, NU);
+            Rd = (rr >= 0 && rr < NU && cc >= 0 && cc < NU) ? x : Rd;
+        }
+        const int kk = r < NU ? r : 0;
+        hk1 = (r < NU) ? 0.5 * (p.sh[ra.oUb + kk] - p.sh[ra.oLb + kk]) : 1.0;
+        const long long bgl = late.bg();
+        const ModelLd<NX, NU> ld(p, bgl);
+        constexpr int REC = NX * NX + NX * NU + NX;
+#pragma unroll
+        for (int a = 0; a < TX; ++a) {
+#pragma unroll
+            for (int b = 0; b < TX; ++b) A[a][b] = ld.A(4 * a + r, 4 * b + c);
+            Bp[a] = ld.B(4 * a + r, c); nBt[a] = -ld.B(4 * a + c, r);
+#pragma unroll
+            for (int qq = 0; qq < SPT; ++qq) { Bpl[qq][a] = ld.B(4 * a + r, c - qq * NUP); nBpl[qq][a] = -Bpl[qq][a]; }
+            const bool v = c == 0 && 4 * a + r < NX;
+            const int ia = v ? 4 * a + r : 0;
+            const double x = p.rec ? p.rec[bgl * REC + NX * NX + NX * NU + ia] : ra.x0[(long long)ia * p.Bsz + bgl];
+            x0r[a] = v ? x : 0.0;
+        }
+        late.park();
+    } else {
+    const ModelLd<NX, NU> ld(p, bg);
 #pragma unroll
     for (int a = 0; a < TX; ++a) {
 #pragma unroll
@@ -359,7 +417,16 @@ __device__ __forceinline__ void r16_setup_mfma(const SetupArgs &p, long long bg,
 #pragma unroll
         for (int qq = 0; qq < SPT; ++qq) { Bpl[qq][a] = ld.B(4 * a + r, c - qq * NUP); nBpl[qq][a] = -Bpl[qq][a]; }
     }
-    const double Rp = (r == c && r >= NU && r < NUP) ? 1.0 : ld.S(p.oR, r, c, NU);   // (a dummy input weighs 1)
+    Rp = (r == c && r >= NU && r < NUP) ? 1.0 : ld.S(p.oR, r, c, NU);   // (a dummy input weighs 1)
+    }
+    // ONE_TRIP: the first half of P (r16_build_P: Lt_N = P_T, Lt_k = Q + A'Lt_{k+1}A; ap = Lt_{k+1} B placed at stage k's columns)
+    double Lt[TX][TX], ap[ONE_TRIP ? NTM : 1][SPT][TX];
+    if constexpr (ONE_TRIP) {
+#pragma unroll
+        for (int a = 0; a < TX; ++a)
+#pragma unroll
+            for (int b = 0; b < TX; ++b) Lt[a][b] = S[a][b];
+    }
 
     // ---- backward sweep: Riccati recursion, the rows rho_k, W by one update per column tile ----
     // LPI = 16: W by 4 x 4 tiles, Wacc[I][J], J <= I.  LPI = 64 (tile I in block I % 4 of register I / 4): the four tiles of a
@@ -412,6 +479,37 @@ __device__ __forceinline__ void r16_setup_mfma(const SetupArgs &p, long long bg,
         constexpr int Ij = T::tile_of_stage(j), off = T::off_of_stage(j), q = off / NUP;
         constexpr bool first_of_tile = (j == N - 1) || (q == SPT - 1);        // (backward: the highest stage of column tile Ij comes first)
         double SA[TX][TX], SB[TX], F[TX], K[TX], Acl[TX][TX], Ktp[TX];
+        if constexpr (ONE_TRIP) {                                     // stage j of P's first half (a chain of its own, in the bubbles of this one)
+            constexpr int Ip = j / SPT, pp = j % SPT;
+#pragma unroll
+            for (int a = 0; a < TX; ++a) {
+                double v = 0.0;
+#pragma unroll
+                for (int k2 = 0; k2 < TX; ++k2) v = mm4(Lt[k2][a], Bpl[pp][k2], v);
+                ap[Ip][pp][a] = v;
+            }
+            if constexpr (j > 0) {
+                double LA[TX][TX];
+#pragma unroll
+                for (int a = 0; a < TX; ++a)
+#pragma unroll
+                    for (int b = 0; b < TX; ++b) {
+                        double v = 0.0;
+#pragma unroll
+                        for (int k2 = 0; k2 < TX; ++k2) v = mm4(Lt[k2][a], A[k2][b], v);
+                        LA[a][b] = v;
+                    }
+#pragma unroll
+                for (int a = 0; a < TX; ++a)
+#pragma unroll
+                    for (int b = 0; b < TX; ++b) {
+                        double v = Q[a][b];
+#pragma unroll
+                        for (int k2 = 0; k2 < TX; ++k2) v = mm4(A[k2][a], LA[k2][b], v);
+                        Lt[a][b] = v;
+                    }
+            }
+        }
 #pragma unroll
         for (int a = 0; a < TX; ++a) {
 #pragma unroll
@@ -563,21 +661,27 @@ __device__ __forceinline__ void r16_setup_mfma(const SetupArgs &p, long long bg,
     coldL = 0u; coldU = 0u;
     if constexpr (ROLL) {
         unsigned bL = 0u, bU = 0u;                                    // lane (r = k, c = 0) of block g: the flags of input k of instance g
-        if (ra.roll) {
+        double At[TX][TX];
+        if (ONE_TRIP || ra.roll) {
             constexpr int REC = NX * NX + NX * NU + NX;
             const double I4 = (r == c) ? 1.0 : 0.0;
-            double At[TX][TX], xr[TX];
+            double xr[TX];
 #pragma unroll
             for (int a = 0; a < TX; ++a) {
 #pragma unroll
                 for (int b = 0; b < TX; ++b) At[b][a] = mm4(A[a][b], I4);          // (A tile)': mm4(At[b][a], x_b) = A_ab x_b
+                if constexpr (ONE_TRIP) xr[a] = x0r[a];
+                else {
                 const bool v = c == 0 && 4 * a + r < NX;
                 const int ia = v ? 4 * a + r : 0;
                 const double x = p.rec ? p.rec[bg * REC + NX * NX + NX * NU + ia] : ra.x0[(long long)ia * p.Bsz + bg];
                 xr[a] = v ? x : 0.0;
+                }
             }
             const int kk = r < NU ? r : 0;
-            const double hk = (r < NU) ? 0.5 * (p.sh[ra.oUb + kk] - p.sh[ra.oLb + kk]) : 1.0;
+            double hk;
+            if constexpr (ONE_TRIP) hk = hk1;
+            else hk = (r < NU) ? 0.5 * (p.sh[ra.oUb + kk] - p.sh[ra.oLb + kk]) : 1.0;
             const unsigned one = (c == 0 && r < NU) ? (1u << r) : 0u;
             sfor<0, N>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
@@ -601,6 +705,43 @@ __device__ __forceinline__ void r16_setup_mfma(const SetupArgs &p, long long bg,
 #pragma unroll
                     for (int a = 0; a < TX; ++a) xr[a] = mm4(nBt[a], un, xn[a]);   // + (-B)(-u_j)
                 }
+            });
+            if constexpr (ONE_TRIP) { bL = ra.roll ? bL : 0u; bU = ra.roll ? bU : 0u; }
+        }
+        if constexpr (ONE_TRIP) {
+            // the second half of P (r16_build_P): the powers X_d = [A^d B | A^(d-1) B | ..], tile (I, I - D) = sum_p ap[I][p]' X_(D SPT + p)
+            wg::ldsd *Pp = Lg + oP;
+            const int dP = oD - oP;
+            double X[TX];
+#pragma unroll
+            for (int a = 0; a < TX; ++a) X[a] = Bpl[0][a];
+            sfor<0, NT>([&](auto Dc) {
+                constexpr int D = decltype(Dc)::value;
+                double acc[NTM];
+#pragma unroll
+                for (int m = 0; m < NTM; ++m) acc[m] = (D == 0) ? Rd : 0.0;
+                sfor<0, SPT>([&](auto pc) {
+                    constexpr int pp = decltype(pc)::value;
+                    constexpr int d = D * SPT + pp;
+                    if constexpr (d > 0) {
+                        double Xn[TX];
+#pragma unroll
+                        for (int a = 0; a < TX; ++a) {
+                            double v = (d <= SPT - 1) ? Bpl[d <= SPT - 1 ? d : 0][a] : 0.0;
+#pragma unroll
+                            for (int k2 = 0; k2 < TX; ++k2) v = mm4(At[k2][a], X[k2], v);
+                            Xn[a] = v;
+                        }
+#pragma unroll
+                        for (int a = 0; a < TX; ++a) X[a] = Xn[a];
+                    }
+                    sfor<D, NT>([&](auto Ic) {
+                        constexpr int I = decltype(Ic)::value;
+#pragma unroll
+                        for (int k2 = 0; k2 < TX; ++k2) acc[I] = mm4(ap[I][pp][k2], X[k2], acc[I]);
+                    });
+                });
+                sfor<D, NT>([&](auto Ic) { constexpr int I = decltype(Ic)::value; store_tile<T, PACKED>(Pp, dP, I, I - D, 2.0 * acc[I], true, r, c); });
             });
         }
         // the flags of instance gq sit in lanes 16 k + 4 gq (k < NU): gather them, hand each instance its own
